@@ -82,6 +82,14 @@ def build_parser():
     ap.add_argument('--config', type=int, default=1)
     ap.add_argument('--views', type=int, default=8)
     ap.add_argument('--ppl', type=int, default=0, help='pixels per lane of the blend kernels (0 = heuristic)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline: the per-kernel table and roofline (an eager pass after the '
+                         'timed region), ms/render and the forward FPS, the CPU baseline, `survey_recipe` and `reference_route` (child '
+                         'runs).  Without it a run sets up, warms up, times --steps steps and prints the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, replay ONE step of the timed path from the seeded start and write what it computed '
+                         '(rendered image and opacity, loss terms, gradients, updated parameters) as DIR/<name>.npy in float32; above 64 MB '
+                         'in all, the large arrays keep a fixed, seeded sample of their rows (benchlib/dump.py)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--list-headroom', type=float, default=1.0,
                     help='multiplies the room the tile lists and the binning capacity get over what the first renders needed (a drifting '

@@ -2,9 +2,10 @@
 
 One measurement = `run(args, env)`: the synthetic scene resident in HBM (`build_scene`), the gradient exchange of a multi-rank
 run (`build_exchange`), the tile-list sizes learnt with the synchronising path (`learn_tile_lists`), the step as eager calls and
-as captured hipGraphs (`build_steps`), warm-up, exactly args.steps timed steps between barriers (benchlib/timing.py), the
-per-kernel pass, BASELINE's second metric (benchlib/render_protocol.py) and the JSON line.  A multi-rank run with no exchange
-flag calls `run` once per exchange variant (benchlib/exchange_rank.py).
+as captured hipGraphs (`build_steps`), warm-up, exactly args.steps timed steps between barriers (benchlib/timing.py), one step's
+outputs from the seeded start (`--dump-outputs`, benchlib/dump.py), with `--full` the per-kernel pass, BASELINE's second metric
+(benchlib/render_protocol.py) and the child runs, and the JSON line.  A multi-rank run with no exchange flag calls `run` once per
+exchange variant (benchlib/exchange_rank.py).
 """
 import json
 import os
@@ -168,7 +169,7 @@ def build_steps(args, env, s, x):
     settings, targets, frames, background = s.settings, s.targets, s.frames, s.background
     compact, sh_factored, pipelined, sh_ex = x.compact, x.sh_factored, x.pipelined, x.sh_ex
     groups = model.param_groups(lr=args.lr)
-    t = SimpleNamespace(fstep=None, opt=None, g_step=None, fused_update=False, train1=None, train_n=None, steps_per_graph=1,
+    t = SimpleNamespace(fstep=None, opt=None, opts=[], g_step=None, fused_update=False, train1=None, train_n=None, steps_per_graph=1,
                         train_chunk=None)
     t.overflow = torch.zeros(1, dtype=torch.int32, device=env.dev)
 
@@ -208,6 +209,7 @@ def build_steps(args, env, s, x):
         optB = FusedAdam([g for g in groups if g['name'] not in ('f_dc', 'f_rest')], eps=1e-15, betas=(0.9, 0.999),
                          zero_after_step=table_span)
         t.lr_schedule = lr_schedules(args, optB)
+        t.opts = [optA, optB]
 
         def part_a(v):
             fstep.backward_raster(*fb_args(v))
@@ -257,7 +259,7 @@ def build_steps(args, env, s, x):
         else:
             from sk_gs_amd.optim import FusedAdam
             opt = FusedAdam(groups, eps=1e-15, betas=(0.9, 0.999), zero_after_step=table_span)
-        t.opt = opt
+        t.opt, t.opts = opt, [opt]
         t.lr_schedule = lr_schedules(args, opt)
         if args.autograd:
             grad_params = [p for p in model.parameters() if p.requires_grad]
@@ -622,6 +624,19 @@ def kernel_table(args, s, t, prof_all, passes):
     return kernels
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+def dump_seeded_step(args, s, t, start, rank):
+    """after the timed region: back to the seeded start (parameters, optimizers at step 0, views rewound), ONE step of the timed path
+    (the same captured graph, or the same eager calls), and its outputs to args.dump_outputs (benchlib/dump.py says why)"""
+    from benchlib import dump
+    dump.restart(s.model, start, t.opts)
+    t.rewind_views()
+    t.train_step(0)
+    torch.cuda.synchronize()
+    if rank == 0:
+        dump.write(args.dump_outputs, dump.last_step_outputs(t.fstep, s.model, dump.cleared_grads(s.model, t.opts)))
+
+
 # ------------------------------------------------------------------------------------------------ one measurement
 def run(args, env):
     """one complete measurement of the workload with the exchange / step options in `args`: builds the scene and the runtime from
@@ -633,6 +648,9 @@ def run(args, env):
     if args.ppl:
         _C.set_pixels_per_lane(args.ppl)
     s = build_scene(args, env)
+    if args.dump_outputs:
+        from benchlib import dump
+        start = dump.snapshot(s.model)  # the seeded parameters, before any step
     x = build_exchange(args, env, s)
     learn_tile_lists(args, s)
     t = build_steps(args, env, s, x)
@@ -697,19 +715,24 @@ def run(args, env):
     assert int(t.overflow.item()) == 0, ('binning capacity overflow during the timed region: result invalid '
                                          + (f'(last step: {st}; tile bucket {s.tile_bucket} slots, R capacity for {s.R_max} x 1.25 x '
                                             f'{_C.config.capacity_growth})' if fstep is not None else ''))
+    if args.dump_outputs:  # (every rank: the replayed step may hold collectives)
+        dump_seeded_step(args, s, t, start, rank)
 
-    passes = min(args.steps, 20)
-    prof_all = timing.profiled_eager_pass(_C, t.eager_step, args.warmup + args.steps, passes)
-    if 'render_backward' not in prof:
-        prof = prof_all
-    kernels = kernel_table(args, s, t, prof_all, passes)
-    if ordered_views:
+    # everything below the timed region's own figures is measured with --full only (an explicit --ms-per-render too)
+    if args.ms_per_render is None:
+        args.ms_per_render = args.full and world == 1
+    kernels = None
+    if args.full:
+        passes = min(args.steps, 20)
+        prof_all = timing.profiled_eager_pass(_C, t.eager_step, args.warmup + args.steps, passes)
+        if 'render_backward' not in prof:
+            prof = prof_all
+        kernels = kernel_table(args, s, t, prof_all, passes)
+    if ordered_views and (args.full or args.ms_per_render):
         view_table.clear_order()  # the measurements below select their views explicitly
         (t.train1 if t.fused_update else t.train_n).set_pre_forward(False)
 
     ms_render, fps = None, None
-    if args.ms_per_render is None:
-        args.ms_per_render = world == 1
     if args.ms_per_render:
         from sk_gs_amd.train_step import GraphedSteps
         ms_render = render_protocol.ms_per_render(model, s.settings[0], H, W, dev)
@@ -782,15 +805,16 @@ def run(args, env):
                    'operator_path_backward_thread': args.backward_thread,
                    'replicas_identical': replicas_identical, 'param_digest': param_digest,
                    'cluster': cluster},
-        'roofline': render_backward_roofline(prof, cfg, s.R_mean, sum(p_.numel() for p_ in model.parameters()), ms_step),
-        'kernels': kernels,
-        'kernels_sum': kernels_sum(kernels, cfg['name'], ms_step),
     }
+    if kernels is not None:
+        line['roofline'] = render_backward_roofline(prof, cfg, s.R_mean, sum(p_.numel() for p_ in model.parameters()), ms_step)
+        line['kernels'] = kernels
+        line['kernels_sum'] = kernels_sum(kernels, cfg['name'], ms_step)
     if ms_render:
         # the same pass as the sum of its kernels' HIP-event times inside the training step (no launch / sync overhead)
         ras = ('preprocess_forward', 'count_tiles', 'scan_tiles', 'scatter', 'tile_sort', 'render_forward', 'render_backward',
                'preprocess_backward')
-        ms_render['kernel_sum'] = round(sum(kernels[k]['us'] * kernels[k]['launches_per_step'] for k in ras if k in kernels) / 1e3, 4)
+        ms_render['kernel_sum'] = None if kernels is None else round(sum(kernels[k]['us'] * kernels[k]['launches_per_step'] for k in ras if k in kernels) / 1e3, 4)
         ms_render['backward_thread'] = args.backward_thread
         ms_render['how'] = ('operator path render() + torch.autograd.grad of (images, opacity) w.r.t. its five inputs, eager '
                             'launches, bucket tile lists, no host synchronisation; kernel_sum: the rasterizer kernels of the '
@@ -799,10 +823,10 @@ def run(args, env):
         line['fps_forward_render'] = fps
     if events is not None:
         line['densify'] = events.record()
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         from benchlib.cpu_baseline import cpu_baseline
         line['cpu_baseline'] = cpu_baseline(cfg, args.cpu_seconds, args.cpu_single_thread, configs=CONFIGS)
-    if (world == 1 and not args.no_cpu_baseline and not args.no_survey_recipe and args.targets == 'own-render' and not args.keep_order
+    if (args.full and world == 1 and not args.no_cpu_baseline and not args.no_survey_recipe and args.targets == 'own-render' and not args.keep_order
             and not args.autograd and not args.eager and args.scale_mult == 1.0):
         line['survey_recipe'] = survey_recipe_run(args)
         if args.config == 1 and not args.no_reference_route:

@@ -126,6 +126,9 @@ def run(args, base_alg_bytes, configs):
     if not args.keep_order:  # Gaussians along a Z-order curve (sk_gs_amd/densify.py::sort_spatially): what a training loop
         from sk_gs_amd.densify import sort_spatially  # does after every densification event
         sort_spatially(model)
+    if args.dump_outputs:
+        from benchlib import dump
+        start = dump.snapshot(model)  # the seeded parameters, before any step
     cams = [scene.make_camera(W, H, seed=i) for i in range(args.views)]
     settings = [scene.raster_settings_from_camera(c, sh_degree=3, colmap=True, device=dev) for c in cams]
     background = torch.ones(3, device=dev)
@@ -212,9 +215,17 @@ def run(args, base_alg_bytes, configs):
     st = step.status()
     assert st['overflow_events'] == 0, 'binning capacity overflow during the timed region: result invalid'
     assert st['pairs_overflow_events'] == 0, 'a superpoint\'s inverse neighbour list overflowed in some step: result invalid'
-    # ---- per-kernel HIP-event timing: an eager pass over the same steps
+    if args.dump_outputs:  # back to the seeded start, ONE step of the timed path, its outputs (benchlib/dump.py)
+        dump.restart(model, start, [opt])
+        if not use_dist:
+            view_table.rewind()
+        train_step(0)
+        torch.cuda.synchronize()
+        if rank == 0:
+            dump.write(args.dump_outputs, dump.last_step_outputs(step, model, dump.cleared_grads(model, [opt])))
+    # ---- with --full: per-kernel HIP-event timing, an eager pass over the same steps
     n_prof = min(args.steps, 20)
-    prof = timing.profiled_eager_pass(_C, eager_step, args.warmup + args.steps, n_prof)
+    prof = timing.profiled_eager_pass(_C, eager_step, args.warmup + args.steps, n_prof) if args.full else {}
     rows_b = 28 * sum(p.numel() for g in opt.param_groups if g.get('name') in train.rows for p in g['params'])
     rest_b = 28 * sum(p.numel() for g in opt.param_groups if g.get('name') in train.rest + train.wide for p in g['params'])
     kernels = {}
@@ -248,7 +259,7 @@ def run(args, base_alg_bytes, configs):
     # forward-only render rate of the stage (the reference's FPS protocol, test.py:102-123: warm-up, then N renders between two
     # events, views cycled): sp net + search + skinning + rasterize as one graph replay per render
     fps = None
-    if world == 1:
+    if args.full and world == 1:
         if not use_dist:
             view_table.clear_order()
         g_fwd = GraphedSteps(lambda _: step.forward(), collect_garbage=False)
@@ -269,7 +280,7 @@ def run(args, base_alg_bytes, configs):
     if rank != 0:
         return None
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline_sp(cfg, M, K, F, min(args.cpu_seconds, 12.0))
         except Exception as e:  # noqa
@@ -284,7 +295,7 @@ def run(args, base_alg_bytes, configs):
     ms_step = elapsed / args.steps * 1e3
     from benchlib.roofline import committed_counter_profile
     from_profile = committed_counter_profile(cfg['name'] + ', stage sp', 'pmc_render_backward_sp.json')
-    return {
+    line = {
         'metric': f'train iters/sec, SUPERPOINT stage (sp net + 3+8-d search + skinning + rasterize fwd+bwd + L1/SSIM loss + Adam; image '
                   f'loss only: the shipped `sparse` / `smooth` weight regularisers are not included), {P // 1000}k Gaussians @{W}x{H}',
         'value': round(world * args.steps / elapsed, 3), 'unit': 'iters/s', 'n_gpus': world, 'steps': args.steps,
@@ -328,3 +339,7 @@ def run(args, base_alg_bytes, configs):
                              'the sp net against the fp32 MFMA peak, the search against its algorithmic bytes'},
         'kernels': kernels,
     }
+    if not args.full:  # (nothing of these was measured)
+        for k in ('cpu_baseline', 'fps_forward_render', 'roofline', 'kernels'):
+            del line[k]
+    return line

@@ -617,6 +617,58 @@ def test_bench_pieces_are_importable_without_a_gpu():
     assert roofline.committed_counter_profile('no-such-workload') is None
 
 
+def test_bench_dump_stays_within_its_limit_and_samples_the_same_rows(tmp_path):
+    """`bench.py --dump-outputs DIR` (benchlib/dump.py): one .npy per array, float32 (float64 kept); when the whole exceeds the limit
+    the arrays of many rows keep a sorted sample of their rows, the same one in every run, and the small ones stay whole"""
+    import numpy as np
+    from benchlib import dump, options
+    args = options.build_parser().parse_args(['--steps', '7', '--dump-outputs', str(tmp_path)])
+    assert args.steps == 7 and args.dump_outputs == str(tmp_path) and args.full is False
+    assert options.build_parser().parse_args(['--full']).full is True
+    big = torch.arange(100_000 * 20, dtype=torch.float32).view(100_000, 20)
+    arrays = {'image': torch.rand(3, 16, 16, dtype=torch.float64), 'loss': torch.tensor([0.5, 0.25, 0.75]),
+              'param.big': big, 'grad.big': -big, 'param.half': torch.ones(10, 2, dtype=torch.float16)}
+    shapes = [dump.write(str(tmp_path / d), arrays, limit=2_000_000) for d in ('a', 'b')]
+    assert shapes[0] == shapes[1] and shapes[0]['image'] == [3, 16, 16] and shapes[0]['param.half'] == [10, 2]
+    got = [{k: np.load(str(tmp_path / d / (k + '.npy'))) for k in arrays} for d in ('a', 'b')]
+    assert sum(x.nbytes for x in got[0].values()) <= 2_000_000
+    assert got[0]['image'].dtype == np.float64 and got[0]['param.half'].dtype == np.float32 and got[0]['loss'].dtype == np.float32
+    rows = got[0]['param.big']
+    assert 0 < rows.shape[0] < 100_000 and np.array_equal(rows, got[1]['param.big'])
+    first = rows[:, 0].astype(np.int64) // 20
+    assert np.all(np.diff(first) > 0) and np.array_equal(rows, big.numpy()[first])
+    # arrays of the same number of rows keep the same rows (a parameter and its gradient stay aligned), listed beside them
+    assert np.array_equal(got[0]['grad.big'], -rows)
+    listed = np.load(str(tmp_path / 'a' / 'sampled_rows.100000.npy'))
+    assert listed.dtype == np.float64 and np.array_equal(listed.astype(np.int64), first)
+    assert dump.write(str(tmp_path / 'c'), {'x': big[:10]})['x'] == [10, 20]   # under the limit: whole
+    # the layout of a config-#1 dump (image, opacity, gradient + parameter of every per-Gaussian tensor): within the 64 MB
+    rows = {'features_rest': (15, 3), 'sp_W': (20,), 'features_dc': (1, 3), 'xyz': (3,), 'scaling': (3,), 'rotation': (4,), 'opacity': (1,)}
+    layout = dict(image=torch.zeros(3, 800, 800), opacity=torch.zeros(800, 800), loss=torch.zeros(3),
+                  **{f'{kind}.{k}': torch.zeros(100_000, *shape) for k, shape in rows.items() for kind in ('grad', 'param')})
+    dump.write(str(tmp_path / 'd'), layout)
+    assert sum(f.stat().st_size for f in (tmp_path / 'd').iterdir()) <= dump.LIMIT_BYTES
+    # the seeded start the dumped step runs from: parameters as first taken, the optimizer at step 0 with zero moments (in place)
+    net = torch.nn.Linear(3, 2)
+    start = dump.snapshot(net)
+    opt = torch.optim.Adam(net.parameters(), lr=0.1)
+    net(torch.ones(5, 3)).sum().backward()
+    opt.step()
+    moments = [st['exp_avg'] for st in opt.state.values()]
+    assert not torch.equal(net.weight.detach(), start[0])
+    dump.restart(net, start, [opt])
+    assert all(torch.equal(p.detach(), s) for p, s in zip(net.parameters(), start))
+    assert all(float(st['step']) == 0 and not st['exp_avg'].any() and not st['exp_avg_sq'].any() for st in opt.state.values())
+    assert all(a is st['exp_avg'] for a, st in zip(moments, opt.state.values()))
+    assert dump.last_step_outputs(None, net).keys() == {'grad.weight', 'grad.bias', 'param.weight', 'param.bias'}
+    assert dump.last_step_outputs(None, net, {'bias'}).keys() == {'grad.weight', 'param.weight', 'param.bias'}
+    assert dump.cleared_grads(net, [opt]) == set()
+    # a multi-rank run that ranks every exchange variant would dump each variant's step in turn: refused before anything starts
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dump-outputs', str(tmp_path / 'x')],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 2 and 'name the exchange' in p.stderr and not (tmp_path / 'x').exists(), p.stderr[-500:]
+
+
 def _gate_row(test, name, v, flips=None):
     r = dict(test=test, name=name, elements=100, tol=1e-4, max_err=v, untraced_max=v)
     if flips is not None:

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/$tag
 rm -rf "$out"; mkdir -p "$out"
 for mode in 1 0 1 0; do
-  SKGS_TILE_ORDER=$mode python bench.py --steps 200 --warmup 20 --no-cpu-baseline --no-ms-per-render $EXTRA 2>/dev/null | python -c "
+  SKGS_TILE_ORDER=$mode python bench.py --full --steps 200 --warmup 20 --no-cpu-baseline --no-ms-per-render $EXTRA 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); k=d['kernels']
 print('order=$mode', d['value'], 'it/s', d['ms_per_step'], 'ms', d['ms_per_step_blocks'], 'fwd', k['render_forward']['us'], 'bwd', k['render_backward']['us'], 'sort', k['tile_sort']['us'])"

@@ -11,7 +11,7 @@ done
 : > $out/summary.txt
 for rep in $(seq 1 $reps); do
   for m in 0 1 2 3; do
-    SKGS_MLP_XCD=$m python bench.py --steps 400 --no-cpu-baseline > $out/bench_${m}_$rep.json 2> $out/bench_${m}_$rep.err
+    SKGS_MLP_XCD=$m python bench.py --full --steps 400 --no-cpu-baseline > $out/bench_${m}_$rep.json 2> $out/bench_${m}_$rep.err
     python - <<P | tee -a $out/summary.txt
 import json
 d=json.loads(open('$out/bench_${m}_$rep.json').read().strip().splitlines()[-1])
