@@ -849,6 +849,22 @@ int skgs_sp_net_backward(const skgs_sp_net* net, const skgs_sp_net* grads, const
     const float* g_d_scale, const float* g_raw, const void* saved, size_t saved_bytes, void* workspace, size_t workspace_bytes,
     const skgs_adam_range* side, skgs_stream_t stream);
 
+/* ---- the same network on P rows: every Gaussian (stages `init_fix` / `init`, sk_gs.py:678-690,741-749,1501-1508) ----
+ * skgs_sp_net with M = P >= 1 rows of `points`, one time for all rows; flags 0 or SKGS_SP_NET_RAW_TIME_DEGREE(d) (0 <= d <= 15);
+ * SKGS_SP_NET_LBS_C (the superpoint stage's epilogue) is refused.  Forward: raw [P,10] ([P,14] with local_w) only -- the rows
+ * of the reference's d_xyz | d_rotation | d_scaling (| g_rotation).  saved: skgs_sp_net_rows_saved_bytes(P) (8448 B per row:
+ * the encoded input and every layer's output), written for the backward, or NULL (a forward without gradients writes only raw).
+ * Backward: WRITES the gradient of every parameter into the pointers of `grads` (points / time ignored) from g_raw [P,10] or
+ * [P,14]; no gradient w.r.t. points or time.  workspace: skgs_sp_net_rows_workspace_bytes(P), no initial contents.  Same inputs,
+ * same bits (the row reduction of the weight gradients is split by P alone and summed in a fixed order).  Four launches forward
+ * and back: one forward (64-row MFMA blocks through the whole network), three backward (row blocks, weight-gradient tiles x
+ * row splits, their ordered sum). */
+size_t skgs_sp_net_rows_saved_bytes(int32_t P);
+size_t skgs_sp_net_rows_workspace_bytes(int32_t P);
+int skgs_sp_net_rows_forward(const skgs_sp_net* net, float* raw, void* saved /* or NULL */, size_t saved_bytes, skgs_stream_t stream);
+int skgs_sp_net_rows_backward(const skgs_sp_net* net, const skgs_sp_net* grads, const float* g_raw, const void* saved,
+    size_t saved_bytes, void* workspace, size_t workspace_bytes, skgs_stream_t stream);
+
 /* ---- densification statistics of one training view (scope row (f)-4) ----
  * networks/sk_gs.py:1990-1997 + networks/gaussian_splatting.py:503-513: for every Gaussian with radii > 0
  *   max_radii2D = max(max_radii2D, radii); xyz_gradient_accum += |grad_means2D[:, :2]|; denom += 1.

@@ -55,7 +55,7 @@ import torch.nn.functional as F
 
 _originals = {}
 calls = {'ssim_fused': 0, 'ssim_reference': 0, 'kinematic_fused': 0, 'kinematic_reference': 0, 'sk_net_fused': 0, 'sk_net_reference': 0,
-         'sp_net_fused': 0, 'sp_net_reference': 0, 'lbs_weight_fused': 0, 'lbs_weight_reference': 0, 'adam_fused': 0, 'adam_reference': 0, 'swizzle_fused': 0,
+         'sp_net_fused': 0, 'sp_net_rows_fused': 0, 'sp_net_reference': 0, 'lbs_weight_fused': 0, 'lbs_weight_reference': 0, 'adam_fused': 0, 'adam_reference': 0, 'swizzle_fused': 0,
          'weight_reg_fused': 0, 'weight_reg_reference': 0, 'adam_tiled': 0}  # counters (tests)
 
 
@@ -240,19 +240,25 @@ def sp_net_shadow(ref):
     return sh
 
 
-SP_NET_MAX_ROWS = 4096   # (a runner keeps 8.6 KB of activations per row and is kept per row count: the superpoint-sized calls only)
+from sk_gs_amd.superpoint import SP_NET_MAX_ROWS  # noqa: E402  (superpoint-sized calls: csrc/sp_mlp.hip; above: sp_net_rows.hip)
 
 
 def deform_network_forward(self, x, t, **kwargs):
-    """``DeformNetwork.forward`` (networks/sk_gs.py:295-317) on the MFMA row-block kernels"""
-    sh = None
+    """``DeformNetwork.forward`` (networks/sk_gs.py:295-317) on the MFMA row-block kernels: up to SP_NET_MAX_ROWS rows (the 512
+    superpoints) on csrc/sp_mlp.hip, above it (every Gaussian: init_stage, the c_net loss, init_superpoints) on csrc/sp_net_rows.hip.
+    The P-row kernels give no gradient w.r.t. the points: a call whose ``x`` requires one keeps the reference's forward, as does a
+    call with one time per row (loss_arap / loss_elastic)"""
+    sh, counter = None, 'sp_net_fused'
     if (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == 3 and not kwargs
-            and 1 <= x.shape[0] <= SP_NET_MAX_ROWS and torch.is_tensor(t) and t.numel() == 1):
-        sh = sp_net_shadow(self)
+            and x.shape[0] >= 1 and torch.is_tensor(t) and t.numel() == 1):
+        if x.shape[0] <= SP_NET_MAX_ROWS:
+            sh = sp_net_shadow(self)
+        elif not x.requires_grad:
+            sh, counter = sp_net_shadow(self), 'sp_net_rows_fused'
     if sh is None:
         calls['sp_net_reference'] += 1
         return _originals['sp_net'](self, x, t, **kwargs)
-    calls['sp_net_fused'] += 1
+    calls[counter] += 1
     return sh(x, t.to(x.device))
 
 

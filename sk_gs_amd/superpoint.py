@@ -35,6 +35,10 @@ import torch.nn.functional as F
 from sk_gs_amd import _C
 from sk_gs_amd.deform_net import freq_encode_torch
 
+# Above this many rows SpDeformNet.forward runs the P-row kernels (csrc/sp_net_rows.hip): 64-row MFMA blocks, per-call buffers owned
+# by the autograd node.  At or below it, the superpoint-sized kernels (csrc/sp_mlp.hip) with a runner kept per row count.
+SP_NET_MAX_ROWS = 4096
+
 
 class SpDeformNet(nn.Module):
     """``DeformNetwork(D, W, is_blender=True, sep_rot=...)`` (networks/sk_gs.py:209-315).  ``sep_rot`` (the class default of the
@@ -127,7 +131,11 @@ class SpDeformNet(nn.Module):
             out.pop('hidden')
             return out
         params = list(self.parameters())
-        out = _SpNetFn.apply(self, x, t, *params)
+        if x.shape[0] > SP_NET_MAX_ROWS:  # every Gaussian (stages init_fix / init): the P-row kernels, nothing kept per row count
+            keep = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+            out = _SpNetRowsFn.apply(self, keep, x, t, *params)
+        else:
+            out = _SpNetFn.apply(self, x, t, *params)
         res = dict(d_xyz=out[0], d_rotation=out[1], d_scaling=out[2])
         if self.sep_rot:
             res['g_rotation'] = out[3]
@@ -265,6 +273,63 @@ class _SpNetFn(torch.autograd.Function):
         for p, k in zip(params, keep):
             p.grad = k
         return (None, None, None, *grads)
+
+
+class _SpNetRowsFn(torch.autograd.Function):
+    """``SpDeformNet`` on P rows (``skgs_sp_net_rows_forward / _backward``).  The buffers are this call's own: ``saved`` (8448 B per
+    row, only when ``keep``: gradients enabled and a parameter requires them) lives on the autograd node, the backward's workspace
+    only during the backward."""
+
+    @staticmethod
+    def forward(ctx, net: SpDeformNet, keep: bool, x: Tensor, t: Tensor, *params):
+        _C._require_gpu(x, 'x')
+        assert net.kernel_supported(), 'csrc/sp_net_rows.hip: 8 x 256 layers, skip after layer 4, degrees 10 / 6, time net 13-256-30'
+        lib = _rows_lib()
+        P = x.shape[0]
+        x = _C._f32c(x.detach(), x.device)
+        tt = _C._f32c(t.detach().reshape(-1)[:1], x.device)
+        raw = torch.empty((P, 14 if net.sep_rot else 10), dtype=torch.float32, device=x.device)
+        saved = torch.empty((int(lib.skgs_sp_net_rows_saved_bytes(C.c_int32(P))),), dtype=torch.uint8, device=x.device) if keep else None
+        d = _net_desc(net, P, x, tt)
+        _C._check(lib.skgs_sp_net_rows_forward(C.byref(d), C.c_void_p(raw.data_ptr()), C.c_void_p(None if saved is None else saved.data_ptr()),
+                                               C.c_size_t(0 if saved is None else saved.numel()), _C._stream()))
+        ctx.net, ctx.P, ctx.saved_rows = net, P, saved
+        if net.sep_rot:
+            return raw[:, 0:3], raw[:, 3:7], raw[:, 7:10], raw[:, 10:14]
+        return raw[:, 0:3], raw[:, 3:7], raw[:, 7:10]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_xyz, g_rot, g_scale, g_loc=None):
+        net, P, saved = ctx.net, ctx.P, ctx.saved_rows
+        if saved is None:
+            raise _C.SkgsError('SpDeformNet: backward through a forward that kept no activations')
+        lib = _rows_lib()
+        dev = saved.device
+        z = lambda g, n: torch.zeros((P, n), device=dev) if g is None else g  # noqa: E731
+        g_raw = torch.cat([z(g_xyz, 3), z(g_rot, 4), z(g_scale, 3)] + ([z(g_loc, 4)] if net.sep_rot else []), dim=1).contiguous()
+        ws = torch.empty((int(lib.skgs_sp_net_rows_workspace_bytes(C.c_int32(P))),), dtype=torch.uint8, device=dev)
+        params = list(net.parameters())
+        keep = [p.grad for p in params]
+        for p in params:  # the kernels WRITE into .grad: hand autograd fresh tensors and restore what was there
+            p.grad = torch.empty_like(p)
+        try:
+            d, dg = _net_desc(net, P, None, None), _net_desc(net, P, None, None, grads=True)
+            _C._check(lib.skgs_sp_net_rows_backward(C.byref(d), C.byref(dg), C.c_void_p(g_raw.data_ptr()), C.c_void_p(saved.data_ptr()),
+                                                    C.c_size_t(saved.numel()), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
+                                                    _C._stream()))
+            grads = [p.grad for p in params]
+        finally:
+            for p, k in zip(params, keep):
+                p.grad = k
+        return (None, None, None, None, *grads)
+
+
+def _rows_lib():
+    lib = _C.load_library()
+    lib.skgs_sp_net_rows_saved_bytes.restype = C.c_size_t
+    lib.skgs_sp_net_rows_workspace_bytes.restype = C.c_size_t
+    return lib
 
 
 class SuperpointGaussians(nn.Module):
