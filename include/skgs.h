@@ -85,6 +85,45 @@ typedef struct skgs_knn_deform_job {
   int32_t largest;      /* skinning alone (joints == NULL) only: see skgs_deform_inputs.largest */
 } skgs_knn_deform_job;
 
+/* Stages init_fix / init (networks/sk_gs.py:741-749,1169-1173) as a job of the rasterizer's per-Gaussian launches: the offset of
+ * every Gaussian comes from the deform network over all P rows (skgs_sp_net_rows_forward), the rest is an activation epilogue:
+ *   means = xyz + d_xyz,  scales = exp(mean(log_scale)) (scales_all_same: the mean over all P x 3 values; per row: over 3),
+ *   rotations = normalize(rot) (eps 1e-12),  opacity = sigmoid(opacity_logit).
+ * Forward (skgs_raster_inputs.offset_job): in global mode a small launch first reduces log_scale in a fixed order (no float atomics)
+ * into *scale_mean; the per-Gaussian launch computes the four tensors in the lane that projects them and writes them to means /
+ * scales / rotations / opacity (which must be the rasterizer's means3D / scales / rotations / opacity).  The image is bit-identical
+ * to the rasterizer without the job fed those tensors.
+ * Backward (skgs_raster_grads.offset_job): the per-Gaussian launch writes g_xyz = dL/dmeans3D, the same into columns 0:3 of g_d_xyz
+ * (the network's g_raw; NULL: not written -- init_fix), g_rot / g_opacity_logit through normalize / sigmoid, and per-workgroup
+ * partials of sum(dL/dscale * scale); a finalize launch sums them in a fixed order and writes sum / (3P) to EVERY element of
+ * g_log_scale (per-row mode: the lane writes its row's sum / 3).  Same inputs, same bits.
+ * Not together with deform_job / deform_backward_job / sp_skinning_job, live_count or cov3D_precomp.  workspace:
+ * skgs_offset_deform_workspace_bytes(P), ZERO before the first call (the library leaves it zero where it must). */
+#define SKGS_OFFSET_SCALE_GLOBAL 0 /* scales_all_same (hard-coded True, sk_gs.py:535) */
+#define SKGS_OFFSET_SCALE_PER_ROW 1
+typedef struct skgs_offset_deform_job {
+  int32_t scale_mode;   /* SKGS_OFFSET_SCALE_GLOBAL / _PER_ROW */
+  int32_t d_xyz_stride; /* floats between rows of d_xyz / g_d_xyz (>= 3): 10 or 14 to read the network's raw rows in place */
+  const float* xyz;           /* [P,3] */
+  const float* d_xyz;         /* [P,stride], columns 0:3 read */
+  const float* log_scale;     /* [P,3] */
+  const float* rot;           /* [P,4] */
+  const float* opacity_logit; /* [P] */
+  float* scale_mean;          /* [1] global mode: the mean of log_scale, written by the forward (not read in per-row mode) */
+  float* means;               /* [P,3]  == skgs_raster_inputs.means3D   (forward) */
+  float* scales;              /* [P,3]  == skgs_raster_inputs.scales    */
+  float* rotations;           /* [P,4]  == skgs_raster_inputs.rotations */
+  float* opacity;             /* [P]    == skgs_raster_inputs.opacity   */
+  float* g_xyz;               /* [P,3]  (backward) */
+  float* g_d_xyz;             /* [P,stride] columns 0:3, or NULL */
+  float* g_log_scale;         /* [P,3] */
+  float* g_rot;               /* [P,4] */
+  float* g_opacity_logit;     /* [P] */
+  void* workspace;
+  size_t workspace_bytes;
+} skgs_offset_deform_job;
+size_t skgs_offset_deform_workspace_bytes(int32_t P);
+
 /* Inputs of rasterize_gaussians / rasterize_gaussians_backward (same meaning, same order as the pybind args). */
 typedef struct skgs_raster_inputs {
   int32_t P;          /* number of Gaussians */
@@ -138,6 +177,8 @@ typedef struct skgs_raster_inputs {
                                * head room): the scatter launch chooses its lanes per Gaussian from it instead of from the CAPACITY
                                * of the tile lists (a bucket layout sized for one long list has many slots per Gaussian and few
                                * tiles per Gaussian: 8 lanes cost that launch 27 us where 4 take 16) */
+  const skgs_offset_deform_job* offset_job; /* NULL, or (forward only): means3D / scales / rotations / opacity are COMPUTED by
+                               * the per-Gaussian launch from this job (see the struct); not with deform_job / live_count */
 } skgs_raster_inputs;
 
 typedef struct skgs_raster_buffers {
@@ -219,6 +260,8 @@ typedef struct skgs_raster_grads {
   const struct skgs_deform_backward_job* deform_backward_job; /* NULL, or: see the struct (below skgs_deform_inputs) */
   const struct skgs_sp_skinning_job* sp_skinning_job;         /* NULL, or: see the struct (beside skgs_sp_skinning_backward);
                                                                  not together with deform_backward_job */
+  const skgs_offset_deform_job* offset_job; /* NULL, or: the backward of the forward's offset_job (see the struct); not together
+                                             * with the two jobs above */
 } skgs_raster_grads;
 size_t skgs_backward_workspace_bytes(int32_t P);
 

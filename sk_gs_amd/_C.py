@@ -36,6 +36,13 @@ class _KnnDeformJob(C.Structure):
         'out_weights', 'means', 'scales', 'rotations', 'opacity')] + [('largest', C.c_int32)]
 
 
+class _OffsetDeformJob(C.Structure):
+    """include/skgs.h: skgs_offset_deform_job (stages init_fix / init)"""
+    _fields_ = [('scale_mode', C.c_int32), ('d_xyz_stride', C.c_int32)] + [(n, C.c_void_p) for n in (
+        'xyz', 'd_xyz', 'log_scale', 'rot', 'opacity_logit', 'scale_mean', 'means', 'scales', 'rotations', 'opacity', 'g_xyz', 'g_d_xyz',
+        'g_log_scale', 'g_rot', 'g_opacity_logit', 'workspace')] + [('workspace_bytes', C.c_size_t)]
+
+
 class _RasterInputs(C.Structure):
     _fields_ = [
         ('P', C.c_int32), ('sh_degree', C.c_int32), ('sh_coeffs', C.c_int32), ('E', C.c_int32),
@@ -48,7 +55,7 @@ class _RasterInputs(C.Structure):
         ('cov3D_precomp', C.c_void_p), ('sh_rest', C.c_void_p), ('background', C.c_void_p),
         ('tile_bucket_capacity', C.c_int32), ('tanfov_device', C.c_void_p),
         ('host_status_words', C.c_int32), ('longest_list_hint', C.c_int32), ('live_count', C.c_void_p),
-        ('deform_job', C.POINTER(_KnnDeformJob)), ('tiles_per_gaussian_hint', C.c_int32),
+        ('deform_job', C.POINTER(_KnnDeformJob)), ('tiles_per_gaussian_hint', C.c_int32), ('offset_job', C.c_void_p),
     ]
 
 
@@ -73,6 +80,7 @@ class _RasterGrads(C.Structure):
         ('workspace_is_zero', C.c_int32), ('dL_dsh_factors', C.c_void_p),
         ('stat_xyz_gradient_accum', C.c_void_p), ('stat_denom', C.c_void_p), ('stat_max_radii2D', C.c_void_p),
         ('stat_grad_multiplier', C.c_float), ('deform_backward_job', C.c_void_p), ('sp_skinning_job', C.c_void_p),
+        ('offset_job', C.c_void_p),
     ]
 
 
@@ -132,7 +140,7 @@ def load_library():
         lib = C.CDLL(_LIB_PATH)
         for name in ('skgs_geom_buffer_bytes', 'skgs_img_buffer_bytes', 'skgs_binning_buffer_bytes',
                      'skgs_backward_workspace_bytes', 'skgs_lbs_deform_backward_workspace_bytes',
-                     'skgs_image_loss_workspace_bytes'):
+                     'skgs_image_loss_workspace_bytes', 'skgs_offset_deform_workspace_bytes'):
             getattr(lib, name).restype = C.c_size_t
         lib.skgs_binning_capacity.restype = C.c_int64
         lib.skgs_binning_capacity.argtypes = [C.c_size_t]

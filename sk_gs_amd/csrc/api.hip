@@ -169,6 +169,7 @@ size_t skgs_img_buffer_bytes(int32_t W, int32_t H) { return img_bytes(W, H); }
 size_t skgs_binning_buffer_bytes(int64_t capacity) { return bin_bytes(capacity < 0 ? 0 : capacity); }
 int64_t skgs_binning_capacity(size_t bytes) { return bin_capacity(bytes); }
 size_t skgs_backward_workspace_bytes(int32_t P) { return (size_t) P * GRAD_ROW * 4 + 256; }
+size_t skgs_offset_deform_workspace_bytes(int32_t P) { return offset_deform_workspace_bytes(P); }
 
 int skgs_rasterize_forward_stage1(const skgs_raster_inputs* in, const skgs_raster_buffers* buf, int32_t* radii,
     int32_t* host_num_rendered, skgs_stream_t stream) {
@@ -235,6 +236,11 @@ int skgs_rasterize_backward(const skgs_raster_inputs* in, const skgs_raster_buff
     const float* out_opacity, const skgs_raster_grads* gr, skgs_stream_t stream) {
   if (check_inputs(in) || check_buffers(in, buf, true)) return 1;
   SKGS_REQUIRE(gr != nullptr, "grads struct is NULL");
+  const skgs_offset_deform_job* oj = gr->offset_job;
+  if (oj) {  // stages init_fix / init: the offset job's backward (the two other jobs serve other stages)
+    SKGS_REQUIRE(!gr->deform_backward_job && !gr->sp_skinning_job, "offset_job: not together with deform_backward_job / sp_skinning_job");
+    if (offset_job_check(*in, *oj, true)) return 1;
+  }
   if (in->P == 0) {  // (the deform backward job's bone gradients are always written completely)
     if (const skgs_deform_backward_job* dj0 = gr->deform_backward_job) {
       SKGS_REQUIRE(dj0->in && dj0->g_bone_T && dj0->g_bone_drot && dj0->g_bone_dscale, "deform_backward_job: NULL argument");
@@ -250,7 +256,7 @@ int skgs_rasterize_backward(const skgs_raster_inputs* in, const skgs_raster_buff
   SKGS_REQUIRE(radii && out_opacity, "radii / out_opacity are required");
   SKGS_REQUIRE(gr->dL_dout_color, "dL_dout_color is required");
   // (with a job attached the per-Gaussian gradients it consumes in registers need no array: any of them may be NULL)
-  SKGS_REQUIRE(gr->dL_dmeans2D && ((gr->deform_backward_job || gr->sp_skinning_job) ||
+  SKGS_REQUIRE(gr->dL_dmeans2D && ((gr->deform_backward_job || gr->sp_skinning_job || oj) ||
                                       (gr->dL_dcolors && gr->dL_dopacity && gr->dL_dmeans3D && gr->dL_dcov3D && gr->dL_dscales &&
                                           gr->dL_drotations)),
       "gradient outputs are required");
@@ -293,6 +299,7 @@ int skgs_rasterize_backward(const skgs_raster_inputs* in, const skgs_raster_buff
     return 1;
   if (launch_preprocess_backward(*in, g, radii, *gr, s)) return 1;
   if (sj) return launch_sp_skinning_rest(*sj, s);
+  if (oj) return launch_offset_scale_grad_finalize(in->P, *oj, s);
   return dj ? launch_deform_backward_finalize(*dj->in, dj->workspace, dj->g_bone_T, dj->g_bone_drot, dj->g_bone_dscale, s) : 0;
 }
 

@@ -302,13 +302,76 @@ __device__ __forceinline__ void stage_rows_out(float* __restrict__ dst, const fl
 // the backward, and projects them from registers: one launch and one round trip through HBM less per step.
 // DK == -1: the skinning alone -- weights / indices are INPUTS (joints == NULL in the public job: the superpoint stage's search has
 // produced them), any number of bones, their rows gathered from global memory (deform_forward_kernel<false>'s arithmetic).
+// DK == -2: stages init_fix / init (skgs_offset_deform_job) -- the offset is an INPUT (columns 0:3 of the network's rows, `stride`
+// floats apart), the scale the exp of one log-scale mean (the device word `scale_mean`, or the lane's own row with `per_row`).
 struct KnnDeformJob {
   int M, K, lds_offset /* floats: where the deform's tables start in the dynamic LDS (behind the SH rows) */;
   int largest;         /* (DK == -1) warp_method `largest`: the position follows the bone of the largest weight alone */
   const float *points, *joints, *sp_W, *bone_T, *bone_drot, *bone_dscale, *xyz, *log_scale, *rot, *opacity_logit;
   int64_t* out_idx;
   float *out_weights, *means, *scales, *rotations, *opacity;
+  int stride, per_row;                     /* (DK == -2) */
+  const float *d_xyz, *scale_mean;         /* (DK == -2) */
 };
+
+// ---- the log-scale mean of stages init_fix / init (global mode): partial sums per workgroup in fp64, the last workgroup out adds
+// them in index order.  The grid is a function of P alone and every sum runs in a fixed order: same inputs, same bits.
+constexpr int OFS_THREADS         = 256;
+constexpr int OFS_MEAN_BLOCKS_MAX = 256;
+static_assert(PRE_BWD_THREADS == OFS_THREADS, "the init job's backward partials are sums over one backward workgroup");
+struct OffsetWs {
+  unsigned* ticket;     // zero between calls
+  double* mean_part;    // [OFS_MEAN_BLOCKS_MAX]
+  double* grad_part;    // [one per backward workgroup]
+};
+inline OffsetWs offset_ws(void* w) {
+  char* p = reinterpret_cast<char*>(w);
+  return OffsetWs{reinterpret_cast<unsigned*>(p), reinterpret_cast<double*>(p + 256), reinterpret_cast<double*>(p + 256 + OFS_MEAN_BLOCKS_MAX * 8)};
+}
+inline int offset_grad_blocks(int P) { return (P + PRE_BWD_THREADS - 1) / PRE_BWD_THREADS; }
+inline int offset_mean_blocks(int P) { return std::max(1, std::min(OFS_MEAN_BLOCKS_MAX, (3 * P + OFS_THREADS * 8 - 1) / (OFS_THREADS * 8))); }
+// sum of v over the OFS_THREADS threads of the workgroup, in a fixed tree order; every thread gets it
+__device__ __forceinline__ double offset_block_sum(double v, double* s) {
+  s[threadIdx.x] = v;
+  __syncthreads();
+#pragma unroll
+  for (int w = OFS_THREADS / 2; w > 0; w >>= 1) {
+    if ((int) threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+    __syncthreads();
+  }
+  return s[0];
+}
+__global__ void __launch_bounds__(OFS_THREADS) offset_scale_mean_kernel(int n, const float* __restrict__ log_scale, OffsetWs ws,
+    float* __restrict__ mean_out) {
+  __shared__ double s[OFS_THREADS];
+  __shared__ unsigned s_last;
+  double a = 0.0;
+  for (int i = blockIdx.x * OFS_THREADS + threadIdx.x; i < n; i += gridDim.x * OFS_THREADS) a += (double) log_scale[i];
+  const double b = offset_block_sum(a, s);
+  if (threadIdx.x == 0) {
+    ws.mean_part[blockIdx.x] = b;
+    __threadfence();  // (the partial before the ticket)
+    s_last = atomicAdd(ws.ticket, 1u) == gridDim.x - 1 ? 1u : 0u;
+  }
+  __syncthreads();
+  if (!s_last) return;
+  __threadfence();
+  double c = 0.0;
+  for (int k = threadIdx.x; k < (int) gridDim.x; k += OFS_THREADS)
+    c += __hip_atomic_load(ws.mean_part + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const double t = offset_block_sum(c, s);
+  if (threadIdx.x == 0) mean_out[0] = (float) (t / (double) n), *ws.ticket = 0u;
+}
+// g_log_scale[every element] = (sum of the backward's partials, in index order) / n: every workgroup adds the same partials in the
+// same order, then fills its part
+__global__ void __launch_bounds__(OFS_THREADS) offset_scale_grad_finalize_kernel(int n, int G, const double* __restrict__ part,
+    float* __restrict__ g_log_scale) {
+  __shared__ double s[OFS_THREADS];
+  double a = 0.0;
+  for (int k = threadIdx.x; k < G; k += OFS_THREADS) a += part[k];
+  const float c = (float) (offset_block_sum(a, s) / (double) n);
+  for (int i = blockIdx.x * OFS_THREADS + threadIdx.x; i < n; i += gridDim.x * OFS_THREADS) g_log_scale[i] = c;
+}
 
 template <bool COLMAP, int DK>
 __global__ void __launch_bounds__(PRE_THREADS) preprocess_forward_kernel(int P, int D, int M, const float* __restrict__ means3D,
@@ -337,7 +400,8 @@ __global__ void __launch_bounds__(PRE_THREADS) preprocess_forward_kernel(int P, 
   float pf_s[3] = {0.f, 0.f, 0.f}, pf_c6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, pf_col[3] = {0.f, 0.f, 0.f};
   float4 pf_q = make_float4(0.f, 0.f, 0.f, 1.f);
   // (DK > 0) the deform's per-Gaussian inputs instead: the point the bones are searched from, and the four raw parameters
-  float dj_p[3] = {0.f, 0.f, 0.f}, dj_x[3] = {0.f, 0.f, 0.f}, dj_ls[3] = {0.f, 0.f, 0.f}, dj_ol = 0.f;
+  // (DK == -2) dj_p is the offset d_xyz, dj_mean the log-scale mean of the global mode
+  float dj_p[3] = {0.f, 0.f, 0.f}, dj_x[3] = {0.f, 0.f, 0.f}, dj_ls[3] = {0.f, 0.f, 0.f}, dj_ol = 0.f, dj_mean = 0.f;
   float4 dj_r4 = make_float4(0.f, 0.f, 0.f, 0.f);
   int sk_j[PREF_K];  // (DK == -1) the first PREF_K (index, weight) pairs of the lane
   float sk_w[PREF_K];
@@ -349,8 +413,19 @@ __global__ void __launch_bounds__(PRE_THREADS) preprocess_forward_kernel(int P, 
         sk_w[q] = q < dj.K ? dj.out_weights[(size_t) ld * dj.K + q] : 0.f;
       }
     }
+    if constexpr (DK == -2) {
 #pragma unroll
-    for (int c = 0; c < 3; ++c) dj_p[c] = dj.points[3 * ld + c], dj_x[c] = dj.xyz[3 * ld + c], dj_ls[c] = dj.log_scale[3 * ld + c];
+      for (int c = 0; c < 3; ++c) dj_p[c] = dj.d_xyz[(size_t) dj.stride * ld + c], dj_x[c] = dj.xyz[3 * ld + c];
+      if (dj.per_row) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dj_ls[c] = dj.log_scale[3 * ld + c];
+      } else {
+        dj_mean = dj.scale_mean[0];
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) dj_p[c] = dj.points[3 * ld + c], dj_x[c] = dj.xyz[3 * ld + c], dj_ls[c] = dj.log_scale[3 * ld + c];
+    }
     dj_r4 = reinterpret_cast<const float4*>(dj.rot)[ld], dj_ol = dj.opacity_logit[ld];
   } else {
     pf_p[0] = means3D[3 * ld], pf_p[1] = means3D[3 * ld + 1], pf_p[2] = means3D[3 * ld + 2];
@@ -452,6 +527,18 @@ __global__ void __launch_bounds__(PRE_THREADS) preprocess_forward_kernel(int P, 
         if (q < dj.K) skin(q, sk_j[q], sk_w[q]);
       for (int k = PREF_K; k < dj.K; ++k) skin(k, (int) dj.out_idx[(size_t) idx * dj.K + k], dj.out_weights[(size_t) idx * dj.K + k]);
       deform_activate_lane(dj_p, sx, sr, ss, dj_x, dj_ls, dj_r4, dj_ol, pf_p, pf_s, pf_q, pf_op);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) dj.means[3 * idx + c] = pf_p[c], dj.scales[3 * idx + c] = pf_s[c];
+      reinterpret_cast<float4*>(dj.rotations)[idx] = pf_q;
+      dj.opacity[idx]                              = pf_op;
+    }
+  }
+  if constexpr (DK == -2) {
+    if (idx < P) {  // init_stage (sk_gs.py:741-749,1169-1173,1202-1203): d_rotation = d_scaling = 0, so the epilogue with zero blends
+      const float m        = dj.per_row ? (dj_ls[0] + dj_ls[1] + dj_ls[2]) / 3.0f : dj_mean;
+      const float zero3[3] = {0.f, 0.f, 0.f}, zero4[4] = {0.f, 0.f, 0.f, 0.f}, ls3[3] = {m, m, m};
+      // (p = 0, sx = d_xyz: means = xyz + (d_xyz - 0) = xyz + d_xyz bit for bit)
+      deform_activate_lane(zero3, dj_p, zero4, zero3, dj_x, ls3, dj_r4, dj_ol, pf_p, pf_s, pf_q, pf_op);
 #pragma unroll
       for (int c = 0; c < 3; ++c) dj.means[3 * idx + c] = pf_p[c], dj.scales[3 * idx + c] = pf_s[c];
       reinterpret_cast<float4*>(dj.rotations)[idx] = pf_q;
@@ -653,7 +740,15 @@ __device__ __forceinline__ void sh_backward(int deg, int M, const float* mean, c
 // the workgroup's partial bone moments, in the LDS the SH rows have just left.
 static_assert(PRE_BWD_THREADS == DEFORM_BWD_THREADS, "the deform backward job runs in this launch's workgroups");
 // JOB 0: none; 1 (DBJ): that; 2 / 3: the superpoint stage's ROWS pass (skgs_raster_grads.sp_skinning_job, sp_rows_lane<8 / 0>
-// of deform_lane.h = the body of sp_backward_rows_kernel) with its bone table in the same LDS.
+// of deform_lane.h = the body of sp_backward_rows_kernel) with its bone table in the same LDS; 4: stages init_fix / init
+// (skgs_raster_grads.offset_job): g_xyz = g_d_xyz = dL/dmean, normalize / sigmoid backward, the workgroup's partial of
+// sum(dL/dscale * scale) for the log-scale mean's backward (offset_scale_grad_finalize_kernel).
+struct OffsetBwdArgs {
+  int stride, per_row;
+  const float *rot, *opacity_logit;
+  float *g_xyz, *g_d_xyz, *g_log_scale, *g_rot, *g_opacity_logit;
+  double* partials;
+};
 template <bool COLMAP, int JOB>
 __global__ void __launch_bounds__(PRE_BWD_THREADS) preprocess_backward_kernel(int P, int D, int M, const float* __restrict__ means3D,
     const int32_t* __restrict__ radii, const float* __restrict__ shs, const float* __restrict__ shs_rest,
@@ -669,7 +764,7 @@ __global__ void __launch_bounds__(PRE_BWD_THREADS) preprocess_backward_kernel(in
     float* __restrict__ dL_dscales, float* __restrict__ dL_drot, float* __restrict__ dL_dextras,
     float* __restrict__ sh_factors /* [P,6] or NULL: see sh_backward */, const float* __restrict__ tanfov_dev,
     const int32_t* __restrict__ live, float* __restrict__ stat_accum, float* __restrict__ stat_denom,
-    float* __restrict__ stat_max_radii, float stat_mult, DeformBwdArgs dbj, SpRowsArgs srj) {
+    float* __restrict__ stat_max_radii, float stat_mult, DeformBwdArgs dbj, SpRowsArgs srj, OffsetBwdArgs obj) {
   constexpr bool DBJ = JOB == 1;
   // (the two device words -- live count, field of view -- and the camera are read BEHIND the per-Gaussian loads below: in front of them
   // each was a round trip of its own before the first of those loads went out; rows up to the launch's P, the capacity, exist)
@@ -709,6 +804,12 @@ __global__ void __launch_bounds__(PRE_BWD_THREADS) preprocess_backward_kernel(in
   }
   DeformBwdLane dbl;  // (DBJ) the deform backward's own per-Gaussian inputs ride in the same round trip
   if constexpr (DBJ) deform_bwd_prefetch(dbj, idx < P_cap ? idx : 0, true, dbl);
+  float4 ob_r4 = make_float4(0.f, 0.f, 0.f, 0.f);  // (JOB 4) the raw rotation and opacity, in the same round trip
+  float ob_ol  = 0.f;
+  if constexpr (JOB == 4) {
+    const int ld = idx < P_cap ? idx : 0;
+    ob_r4 = reinterpret_cast<const float4*>(obj.rot)[ld], ob_ol = obj.opacity_logit[ld];
+  }
   const float cam_v = threadIdx.x < 16 ? viewmatrix[threadIdx.x] : 0.f, cam_p = threadIdx.x < 16 ? projmatrix[threadIdx.x] : 0.f;
   const float cam_c = threadIdx.x < 3 ? campos[threadIdx.x] : 0.f;
   if (live) P = min(P, live[0]);  // the number of Gaussians is a device word: one captured graph survives densification
@@ -1013,7 +1114,46 @@ __global__ void __launch_bounds__(PRE_BWD_THREADS) preprocess_backward_kernel(in
     __syncthreads();  // the SH rows have left the LDS: it is the deform backward's now
     deform_bwd_moments(dbj, P, s_sh, dbl, dj_gm, dj_gs, dj_gr, dj_go);
   }
-  if constexpr (JOB >= 2) {
+  if constexpr (JOB == 4) {
+    double term = 0.0;
+    if (idx < P) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) obj.g_xyz[3 * idx + c] = dj_gm[c];
+      if (obj.g_d_xyz)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) obj.g_d_xyz[(size_t) obj.stride * idx + c] = dj_gm[c];
+      // normalize(rot + 0) backward (eps 1e-12) and sigmoid backward: deform_bwd_moments' expressions
+      const float v[4]  = {ob_r4.x + 0.f, ob_r4.y + 0.f, ob_r4.z + 0.f, ob_r4.w + 0.f};
+      const float gr[4] = {dj_gr.x, dj_gr.y, dj_gr.z, dj_gr.w};
+      const float nv    = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
+      float g_v[4];
+      if (nv > 1e-12f) {
+        const float uq[4] = {v[0] / nv, v[1] / nv, v[2] / nv, v[3] / nv};
+        const float dot   = uq[0] * gr[0] + uq[1] * gr[1] + uq[2] * gr[2] + uq[3] * gr[3];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) g_v[c] = (gr[c] - uq[c] * dot) / nv;
+      } else {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) g_v[c] = gr[c] / 1e-12f;
+      }
+      reinterpret_cast<float4*>(obj.g_rot)[idx] = make_float4(g_v[0], g_v[1], g_v[2], g_v[3]);
+      const float sg           = 1.0f / (1.0f + expf(-ob_ol));
+      obj.g_opacity_logit[idx] = dj_go * sg * (1.0f - sg);
+      // scales = exp(mean): d loss / d mean = sum over the Gaussian's three scales of dL/dscale * scale
+      const float t = dj_gs[0] * pf_s[0] + dj_gs[1] * pf_s[1] + dj_gs[2] * pf_s[2];
+      if (obj.per_row) {
+        const float r = t / 3.0f;
+        obj.g_log_scale[3 * idx] = r, obj.g_log_scale[3 * idx + 1] = r, obj.g_log_scale[3 * idx + 2] = r;
+      }
+      term = (double) t;
+    }
+    if (!obj.per_row) {
+      __shared__ double s_red[OFS_THREADS];
+      const double b = offset_block_sum(term, s_red);
+      if (threadIdx.x == 0) obj.partials[blockIdx.x] = b;
+    }
+  }
+  if constexpr (JOB == 2 || JOB == 3) {
     __syncthreads();
     for (int j = threadIdx.x; j < srj.M; j += PRE_BWD_THREADS) load_bone(srj.bone_T, srj.bone_drot, srj.bone_dscale, j, s_sh + j * BONE_F);
     __syncthreads();
@@ -1103,10 +1243,48 @@ __global__ void mark_visible_kernel(int P, const float* means, const float* view
 
 }  // namespace
 
+size_t offset_deform_workspace_bytes(int P) {
+  return 256 + (size_t) OFS_MEAN_BLOCKS_MAX * 8 + align256((size_t) offset_grad_blocks(P > 1 ? P : 1) * 8);
+}
+
+// the arguments of an offset job (skgs_offset_deform_job) for the forward (backward = false) or the backward of `in`
+int offset_job_check(const skgs_raster_inputs& in, const skgs_offset_deform_job& j, bool backward) {
+  SKGS_REQUIRE(j.scale_mode == SKGS_OFFSET_SCALE_GLOBAL || j.scale_mode == SKGS_OFFSET_SCALE_PER_ROW, "offset_job: scale_mode %d",
+      j.scale_mode);
+  SKGS_REQUIRE(j.d_xyz_stride >= 3, "offset_job: d_xyz_stride %d < 3", j.d_xyz_stride);
+  SKGS_REQUIRE(in.live_count == nullptr, "offset_job: no row capacity (live_count)");
+  SKGS_REQUIRE(in.cov3D_precomp == nullptr, "offset_job: not with cov3D_precomp");
+  const bool global = j.scale_mode == SKGS_OFFSET_SCALE_GLOBAL;
+  SKGS_REQUIRE(!global || (j.workspace && j.workspace_bytes >= offset_deform_workspace_bytes(in.P)),
+      "offset_job: workspace NULL or too small (skgs_offset_deform_workspace_bytes)");
+  SKGS_REQUIRE(j.rot && j.opacity_logit, "offset_job: NULL pointer");
+  if (!backward) {
+    SKGS_REQUIRE(in.deform_job == nullptr, "offset_job: not together with deform_job");
+    SKGS_REQUIRE(j.xyz && j.d_xyz && j.log_scale && j.means && j.scales && j.rotations && j.opacity && (!global || j.scale_mean),
+        "offset_job: NULL pointer");
+    SKGS_REQUIRE(j.means == in.means3D && j.scales == in.scales && j.rotations == in.rotations && j.opacity == in.opacity,
+        "offset_job: means / scales / rotations / opacity must be the rasterizer's means3D / scales / rotations / opacity");
+  } else {
+    SKGS_REQUIRE(j.g_xyz && j.g_log_scale && j.g_rot && j.g_opacity_logit, "offset_job: NULL pointer");
+    SKGS_REQUIRE(in.scales && in.rotations, "offset_job: not with cov3D_precomp");
+  }
+  return 0;
+}
+
+int launch_offset_scale_grad_finalize(int P, const skgs_offset_deform_job& j, hipStream_t s) {
+  if (P == 0 || j.scale_mode != SKGS_OFFSET_SCALE_GLOBAL) return 0;
+  const int n = 3 * P;
+  hipLaunchKernelGGL(offset_scale_grad_finalize_kernel, dim3(std::min(1024, (n + OFS_THREADS - 1) / OFS_THREADS)), dim3(OFS_THREADS), 0, s,
+      n, offset_grad_blocks(P), offset_ws(j.workspace).grad_part, j.g_log_scale);
+  SKGS_CHECK_HIP(hipGetLastError());
+  return 0;
+}
+
 int launch_preprocess_forward(const skgs_raster_inputs& in, GeomView g, ImgView im, int32_t* radii, hipStream_t s) {
   const int P = in.P;
   const float focal_y = in.image_height / (2.0f * in.tanfovy);
   const float focal_x = in.image_width / (2.0f * in.tanfovx);
+  if (in.offset_job && offset_job_check(in, *in.offset_job, false)) return 1;
   if (P == 0) return fill_u32(im.tile_counts, 0u, (size_t) im.T, s) || fill_u32(im.cursors, 0u, (size_t) im.T, s);
   ProfScope prof(K_PREPROCESS_FWD, s);
   const bool bucket = in.tile_bucket_capacity > 0;
@@ -1145,6 +1323,17 @@ int launch_preprocess_forward(const skgs_raster_inputs& in, GeomView g, ImgView 
     // 32 us instead of 22)
     if (search) lds = ((size_t) dj.lds_offset + (size_t) ((j->M * 3 + 3) & ~3) + ((j->M * BONE_F + 3) & ~3)) * 4;
   }
+  if (const skgs_offset_deform_job* j = in.offset_job) {  // stages init_fix / init: (the log-scale mean, then) the epilogue in the lane
+    dk = -2;
+    dj.stride = j->d_xyz_stride, dj.per_row = j->scale_mode == SKGS_OFFSET_SCALE_PER_ROW ? 1 : 0;
+    dj.d_xyz = j->d_xyz, dj.scale_mean = j->scale_mean, dj.xyz = j->xyz, dj.log_scale = j->log_scale, dj.rot = j->rot;
+    dj.opacity_logit = j->opacity_logit, dj.means = j->means, dj.scales = j->scales, dj.rotations = j->rotations, dj.opacity = j->opacity;
+    if (!dj.per_row) {
+      hipLaunchKernelGGL(offset_scale_mean_kernel, dim3(offset_mean_blocks(P)), dim3(OFS_THREADS), 0, s, 3 * P, j->log_scale,
+          offset_ws(j->workspace), j->scale_mean);
+      SKGS_CHECK_HIP(hipGetLastError());
+    }
+  }
 #define SKGS_PRE_FWD(COLMAP_, DK_)                                                                                          \
   hipLaunchKernelGGL((preprocess_forward_kernel<COLMAP_, DK_>), grid, block, lds, s, P, in.sh_degree, in.sh_coeffs, in.means3D, \
       in.scales, in.scale_modifier, in.rotations, in.opacity, in.sh, in.sh_rest, in.cov3D_precomp, in.colors_precomp,        \
@@ -1156,6 +1345,8 @@ int launch_preprocess_forward(const skgs_raster_inputs& in, GeomView g, ImgView 
       SKGS_PRE_FWD(true, 0);
     else if (dk == -1)
       SKGS_PRE_FWD(true, -1);
+    else if (dk == -2)
+      SKGS_PRE_FWD(true, -2);
     else if (dk == 5)
       SKGS_PRE_FWD(true, 5);
     else
@@ -1165,6 +1356,8 @@ int launch_preprocess_forward(const skgs_raster_inputs& in, GeomView g, ImgView 
       SKGS_PRE_FWD(false, 0);
     else if (dk == -1)
       SKGS_PRE_FWD(false, -1);
+    else if (dk == -2)
+      SKGS_PRE_FWD(false, -2);
     else if (dk == 5)
       SKGS_PRE_FWD(false, 5);
     else
@@ -1198,6 +1391,11 @@ int launch_preprocess_backward(const skgs_raster_inputs& in, GeomView g, const i
     srj = sp_rows_args(*j);
     lds = std::max(lds, sp_rows_lds_bytes(j->in->M));
   }
+  OffsetBwdArgs obj{};
+  if (const skgs_offset_deform_job* j = gr.offset_job) {  // (checked by skgs_rasterize_backward)
+    obj = OffsetBwdArgs{j->d_xyz_stride, j->scale_mode == SKGS_OFFSET_SCALE_PER_ROW ? 1 : 0, j->rot, j->opacity_logit, j->g_xyz,
+        j->g_d_xyz, j->g_log_scale, j->g_rot, j->g_opacity_logit, j->workspace ? offset_ws(j->workspace).grad_part : nullptr};
+  }
 #define SKGS_PB_ARGS                                                                                                     \
   P, in.sh_degree, in.sh_coeffs, in.means3D, radii, in.sh, in.sh_rest, in.scales, in.rotations, in.scale_modifier,        \
       in.cov3D_precomp, in.viewmatrix, in.projmatrix, in.campos, in.image_width, in.image_height, in.tanfovx, in.tanfovy, \
@@ -1205,8 +1403,8 @@ int launch_preprocess_backward(const skgs_raster_inputs& in, GeomView g, const i
       gr.grad_means2D_in, gr.grad_conic_in, gr.grad_opacity_in, E, gr.dL_dmeans2D, gr.dL_dconic, gr.dL_dcolors,           \
       gr.dL_dopacity, gr.dL_dmeans3D, gr.dL_dcov3D, gr.dL_dsh, gr.dL_dsh_rest, gr.dL_dscales, gr.dL_drotations,           \
       gr.dL_dextras, gr.dL_dsh_factors, in.tanfov_device, in.live_count, gr.stat_xyz_gradient_accum, gr.stat_denom,        \
-      gr.stat_max_radii2D, (gr.stat_grad_multiplier != 0.f ? gr.stat_grad_multiplier : 1.0f), dbj, srj
-  const int job = gr.deform_backward_job ? 1 : gr.sp_skinning_job ? (gr.sp_skinning_job->F == 8 ? 2 : 3) : 0;
+      gr.stat_max_radii2D, (gr.stat_grad_multiplier != 0.f ? gr.stat_grad_multiplier : 1.0f), dbj, srj, obj
+  const int job = gr.deform_backward_job ? 1 : gr.sp_skinning_job ? (gr.sp_skinning_job->F == 8 ? 2 : 3) : gr.offset_job ? 4 : 0;
 #define SKGS_PB(JOB_)                                                                                  \
   if (in.colmap)                                                                                       \
     hipLaunchKernelGGL((preprocess_backward_kernel<true, JOB_>), grid, block, lds, s, SKGS_PB_ARGS);   \
@@ -1216,6 +1414,7 @@ int launch_preprocess_backward(const skgs_raster_inputs& in, GeomView g, const i
     case 1: SKGS_PB(1); break;
     case 2: SKGS_PB(2); break;
     case 3: SKGS_PB(3); break;
+    case 4: SKGS_PB(4); break;
     default: SKGS_PB(0); break;
   }
 #undef SKGS_PB

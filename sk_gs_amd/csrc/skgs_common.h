@@ -437,6 +437,9 @@ int launch_preprocess_backward(const skgs_raster_inputs& in, GeomView g, const i
 int launch_sh_grad_from_factors(int P, int n_views, int D, int M, const float* factors, float* dL_dsh, float* dL_dsh_rest,
     hipStream_t s);
 int launch_mark_visible(int P, const float* means, const float* view, int colmap, uint8_t* present, hipStream_t s);
+size_t offset_deform_workspace_bytes(int P);
+int offset_job_check(const skgs_raster_inputs& in, const skgs_offset_deform_job& j, bool backward);
+int launch_offset_scale_grad_finalize(int P, const skgs_offset_deform_job& j, hipStream_t s);
 // binning.hip
 int launch_scan_tiles(GeomView g, ImgView im, int64_t P, hipStream_t s);  // count tiles (16 lanes / Gaussian) + scan
 int launch_scatter_sort(const skgs_raster_inputs& in, GeomView g, ImgView im, BinView b, hipStream_t s);

@@ -23,7 +23,7 @@ bone-moment finalize | skeleton backward) behind those two methods, on the model
   copy slower.
 
 Conditions of the fast path (anything else runs the reference's own ``render``; ``calls`` counts both and ``why_not`` keeps the last
-reason): stage ``sk`` or ``sp``; training with grad enabled; ONE view; ``t`` / ``time_id`` / ``info`` tensors on the HIP device; no ``hook``
+reason): stage ``sk``, ``sp``, ``init_fix`` or ``init``; training with grad enabled; ONE view; ``t`` / ``time_id`` / ``info`` tensors on the HIP device; no ``hook``
 (other keywords are ignored, as the reference's ``render`` ignores them); ``use_official_gaussians_render`` (the shipped configs), no
 ``convert_SHs_python`` / ``compute_cov3D``; a background of <= 3 values.  Stage ``sk``: the skeleton is initialised; ``LBS_method == 'W'``
 with ``sp_W`` [P, M] over the M <= 48 joints, ``num_knn`` <= 8; quaternion rotations, no ``sk_feature``; a ``SimpleDeformationNetwork`` the
@@ -32,7 +32,9 @@ matrix (their ``.data`` become row views of it: same Parameter objects, same val
 ``sp`` (``FusedSuperpointStep``): 60 < M <= 1024 superpoints, ``num_knn`` <= 8, 0 or 8 hyper dimensions, any of the four weightings,
 ``warp_method`` LBS / LBS_c / largest, ``sep_rot`` either way, ``is_blender=True``; ``outputs['_knn_w']`` and ``outputs['_spT']`` are outputs
 of the node too -- the shipped ``sparse`` / ``smooth`` regularisers and the joint losses differentiate them (sk_gs.py:1555-1574) -- and their
-cotangents enter the backward half (``skgs_sp_skinning_job.g_weights_extra``; ``g_bone_T`` before the network's backward).
+cotangents enter the backward half (``skgs_sp_skinning_job.g_weights_extra``; ``g_bone_T`` before the network's backward).  Stages
+``init_fix`` / ``init`` (``init_stage.FusedInitStep``): P >= 1, an ``sp_deform_net`` the P-row kernels cover with ``is_blender=True``, no positive
+``p_arap_ct_init`` weight; the dict holds ``images``, ``viewspace_points``, ``radii``, ``points``, ``stage``; a refusal names the stage.
 
 The forward half and the backward half are ONE hipGraph replay each (``SKGS_REF_FUSED_GRAPHS=0``: the same launches issued one by one);
 per call the host still issues the slot fill, the target's layout copy and the two loss launches.  Nothing blocks on the device per
@@ -247,6 +249,55 @@ def _conditions_sp(ref):
     return None
 
 
+class _ModelViewInit:
+    """what ``FusedInitStep`` asks of a model, answered by the reference's model in stage init_fix / init"""
+    static, capacity, sk_deform_net, M, K = False, None, None, 1, 1
+
+    def __init__(self, ref, shadow_net, stage):
+        self._ref, self.sp_deform_net, self.stage = ref, shadow_net, stage
+        for name in ('_xyz', '_features_dc', '_features_rest', '_scaling', '_rotation', '_opacity'):
+            setattr(self, name, getattr(ref, name))
+        self.P, self.max_sh_degree = int(ref._xyz.shape[0]), int(ref.max_sh_degree)
+
+    def topology(self):
+        return {}
+
+    def parameters(self):
+        # init_fix detaches d_xyz: no network parameter gets a gradient; init: every one but the heads the stage never reads
+        # (gaussian_rotation / gaussian_scaling / local_rotation: their .grad stays None in the reference, sk_gs.py:741-749)
+        ps = [self._xyz, self._features_dc, self._features_rest, self._scaling, self._rotation, self._opacity]
+        if self.stage == 'init':
+            from sk_gs_amd.init_stage import trained_net_parameters
+            ps += trained_net_parameters(self.sp_deform_net)
+        return ps
+
+
+def _conditions_init(ref):
+    """None when ``ref`` in stage init_fix / init is what ``FusedInitStep`` covers, else the reason (the device test comes last: on a
+    host without a GPU every other condition has been checked when it refuses)"""
+    from sk_gs_amd import reference_accel as ra
+    if not getattr(ref, 'use_official_gaussians_render', False):
+        return 'use_official_gaussians_render is off (the in-tree rasterizer convention: operator path)'
+    if getattr(ref, 'convert_SHs_python', False) or getattr(ref, 'compute_cov3D', False):
+        return 'convert_SHs_python / compute_cov3D'
+    if not getattr(ref.sp_deform_net, 'is_blender', False):
+        return 'sp_deform_net without the time network (its per-call time noise, sk_gs.py:742-744, stays with the reference)'
+    sh = ra.sp_net_shadow(ref.sp_deform_net)
+    if sh is None or not sh.kernel_supported():
+        return 'sp_deform_net is not a network the row-block kernels cover'
+    lf = getattr(ref, 'loss_funcs', None)
+    if lf is not None and hasattr(lf, 'w') and float(lf.w('p_arap_ct_init')) > 0:
+        return 'p_arap_ct_init differentiates outputs[\'points\'] (sk_gs.py:1548)'
+    ps = [ref._xyz, ref._features_dc, ref._features_rest, ref._scaling, ref._rotation, ref._opacity]
+    if not all(torch.is_tensor(p) for p in ps) or int(ref._xyz.shape[0]) == 0:
+        return f'shapes: P = {int(ref._xyz.shape[0]) if torch.is_tensor(ref._xyz) else None}'
+    if not all(p.dtype == torch.float32 and p.is_contiguous() for p in ps):
+        return 'parameters are not contiguous fp32 tensors'
+    if not all(p.is_cuda for p in ps) or not all(q.is_cuda for q in sh.parameters()):
+        return 'parameters are not on a HIP device'
+    return None
+
+
 class FusedReferenceRoute:
     """one reference model's fused step for one stage: the adapter, the ``FusedViewStep`` / ``FusedSuperpointStep``, the persistent
     gradients, the graphs"""
@@ -265,6 +316,9 @@ class FusedReferenceRoute:
             self.shadow = shadow
             topo = ra._topology(ref.joint_parents, ref.joint_root)
             self.view = _ModelView(ref, shadow, topo)
+        elif stage in _INIT_STAGES:
+            self.shadow = ra.sp_net_shadow(ref.sp_deform_net)
+            self.view = _ModelViewInit(ref, self.shadow, stage)
         else:
             self.shadow = ra.sp_net_shadow(ref.sp_deform_net)
             self.view = _ModelViewSp(ref, self.shadow)
@@ -331,6 +385,10 @@ class FusedReferenceRoute:
             from sk_gs_amd.superpoint import FusedSuperpointStep
             step = FusedSuperpointStep(self.view, self.W, self.H, capacity=max(24 * self.view.P, 64 * T) if bucket == 0 else 0,
                                        lambda_dssim=0.2, background=bg, tile_bucket=bucket, view_table=self.table)
+        elif self.stage in _INIT_STAGES:
+            from sk_gs_amd.init_stage import FusedInitStep
+            step = FusedInitStep(self.view, self.W, self.H, capacity=max(24 * self.view.P, 64 * T) if bucket == 0 else 0, stage=self.stage,
+                                 lambda_dssim=0.2, background=bg, tile_bucket=bucket, view_table=self.table)
         else:
             step = FusedViewStep(self.view, self.W, self.H, capacity=max(24 * self.view.P, 64 * T) if bucket == 0 else 0, lambda_dssim=0.2,
                                  background=bg, tile_bucket=bucket, view_table=self.table)
@@ -508,6 +566,8 @@ class FusedReferenceRoute:
             image = _FusedRender.apply(self, self.view._xyz)                 # [3,H,W]
             out['_knn_w'] = st.weights.unsqueeze(0)
             out['_skT'], out['_sk_rot'], out['_sk_scale'] = st.bone_T.unsqueeze(0), st._d_rot.unsqueeze(0), st._d_scale.unsqueeze(0)
+        elif self.stage in _INIT_STAGES:                                     # (forward returns no `_` entries in these stages)
+            image = _FusedRender.apply(self, self.view._xyz)
         else:
             # outputs['_knn_w'] and outputs['_spT'] carry gradient in the reference (the `sparse` / `smooth` regularisers and the joint
             # losses read them, sk_gs.py:1555-1574): outputs of the node; their cotangents enter the backward half
@@ -525,7 +585,8 @@ class FusedReferenceRoute:
         out['viewspace_points'] = [self.vp]
         out['radii'] = st.radii.unsqueeze(0)
         out['points'] = st.means.unsqueeze(0)
-        out['_knn_i'] = st.indices.unsqueeze(0)
+        if self.stage not in _INIT_STAGES:
+            out['_knn_i'] = st.indices.unsqueeze(0)
         out['stage'] = stage
         calls['render_fused'] += 1
         return out
@@ -786,9 +847,12 @@ def _size_of(info, cached):
     return int(w), int(h)
 
 
+_INIT_STAGES = ('init_fix', 'init')
+
+
 def _route_for(self, stage, t, info, background, time_id, scale_modifier, args, kwargs):
-    if stage not in ('sk', 'sp'):
-        return None, f'stage {stage!r} (the fused route covers sk and sp)'
+    if stage not in ('sk', 'sp') + _INIT_STAGES:
+        return None, f'stage {stage!r} (the fused route covers sk, sp, init_fix and init)'
     if not (self.training and torch.is_grad_enabled()):
         return None, 'not training / grad disabled'
     if 'hook' in kwargs:      # (the only keyword the reference's render reads besides its named ones, sk_gs.py:1222-1223: it edits the
@@ -818,7 +882,7 @@ def _route_for(self, stage, t, info, background, time_id, scale_modifier, args, 
     if cached is not None and (cached.light != _light_identity(self, stage) or (cached.W, cached.H) != (W, H)):
         cached = None
     if cached is None:
-        reason = _conditions(self) if stage == 'sk' else _conditions_sp(self)
+        reason = _conditions(self) if stage == 'sk' else _conditions_sp(self) if stage == 'sp' else _conditions_init(self)
         if reason is not None:
             per_stage[stage] = (reason, _light_identity(self, stage))
             return None, reason
@@ -831,7 +895,9 @@ def _route_for(self, stage, t, info, background, time_id, scale_modifier, args, 
 _LIGHT = {'sk': ('_xyz', '_features_dc', '_features_rest', '_scaling', '_rotation', '_opacity', 'sp_W', 'joints', 'global_tr', 'sk_cache',
                  'joint_parents', 'sk_deform_net', 'sk_is_init'),
           'sp': ('_xyz', '_features_dc', '_features_rest', '_scaling', '_rotation', '_opacity', 'sp_W', 'sp_points', 'hyper_feature',
-                 'sp_hyper_feature', '_sp_radius', '_sp_weight', 'sp_deform_net')}
+                 'sp_hyper_feature', '_sp_radius', '_sp_weight', 'sp_deform_net'),
+          'init': ('_xyz', '_features_dc', '_features_rest', '_scaling', '_rotation', '_opacity', 'sp_deform_net'),
+          'init_fix': ('_xyz', '_features_dc', '_features_rest', '_scaling', '_rotation', '_opacity', 'sp_deform_net')}
 
 
 def _light_identity(ref, stage='sk'):
@@ -840,6 +906,8 @@ def _light_identity(ref, stage='sk'):
     version, the skeleton flag's"""
     obj = tuple(id(getattr(ref, n, None)) for n in _LIGHT[stage])
     x = ref._xyz
+    if stage in _INIT_STAGES:
+        return obj + (x.data_ptr(), int(x.shape[0]))
     if stage == 'sp':
         return obj + (x.data_ptr(), int(x.shape[0]), int(ref.sp_points.shape[0]), int(getattr(ref, 'num_knn', 0)),
                       getattr(ref, 'LBS_method', None), getattr(ref, 'warp_method', None), bool(getattr(ref, 'sep_rot', False)))
@@ -867,6 +935,8 @@ def render(self, *args, t=None, info, background=None, time_id=None, scale_modif
     stage = self.get_now_stage(stage)
     route, reason = _route_for(self, stage, t, info, background, time_id, scale_modifier, args, kwargs)
     if route is None:
+        if stage in _INIT_STAGES and not reason.startswith('stage '):
+            reason = f'stage {stage!r}: {reason}'
         why_not['render'] = reason
         calls['render_reference'] += 1
         return ra._originals['render'](self, *args, t=t, info=info, background=background, time_id=time_id, scale_modifier=scale_modifier,
