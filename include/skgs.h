@@ -818,6 +818,14 @@ typedef struct skgs_sp_skinning_job {
   const float* g_weights_extra; /* NULL, or [P,K]: a cotangent on the LBS weights from OUTSIDE the skinning -- the reference's loss
                                  * reads outputs['_knn_w'] in stage `sp` (`sparse`, `smooth`: networks/sk_gs.py:1339-1359,1572-1574) --
                                  * added to the skinning's own before the weighting's chain rule (and into g_weights) */
+  int32_t image_to_deform_off;  /* 0: stage `sp` (every zero-initialised caller).  Non-zero: stage `sp_fix`, where the reference
+                                 * detaches the network's offsets (networks/sk_gs.py:1174-1178: d_xyz, d_rotation, d_scaling.detach()):
+                                 * the upstream gradients reach g_xyz, g_log_scale, g_rot, g_opacity_logit only.  Without
+                                 * g_weights_extra nothing else runs -- g_weights, g_feature, the superpoint gradients and the
+                                 * workspace are not written, no bones / finalize launch follows (in skgs_rasterize_backward: one
+                                 * per-Gaussian launch with no bone table in LDS).  With g_weights_extra the full pass runs on that
+                                 * cotangent ALONE (g_weights = g_weights_extra; the skinning's own part and the payload of the bones
+                                 * pass are zero), so the superpoint gradients are those of the weighting only. */
 } skgs_sp_skinning_job;
 int skgs_sp_skinning_backward(const skgs_deform_inputs* in, int32_t F, const float* feature, const float* sp_feature,
     const float* sp_radius_raw, const float* sp_weight_raw, float temperature, int32_t logit_weighting, const float* nn_dist,
@@ -825,6 +833,10 @@ int skgs_sp_skinning_backward(const skgs_deform_inputs* in, int32_t F, const flo
     float* g_log_scale, float* g_rot, float* g_opacity_logit, float* g_feature, float* g_bone_T, float* g_bone_drot,
     float* g_bone_dscale, float* g_sp_feature, float* g_sp_radius, float* g_sp_weight, void* pairs, size_t pairs_bytes,
     void* workspace, size_t workspace_bytes, skgs_stream_t stream);
+/* skgs_sp_skinning_backward with its arguments as the job struct: the same launches, and the two fields the call above has no
+ * parameter for -- g_weights_extra and image_to_deform_off -- act as in skgs_rasterize_backward. */
+int skgs_sp_skinning_backward_job(const skgs_sp_skinning_job* job, const float* g_means, const float* g_scales, const float* g_rotations,
+    const float* g_opacity, skgs_stream_t stream);
 
 /* ---- the deform network of the SUPERPOINT stage (stage `sp`, networks/sk_gs.py:830-856) ----
  * sp_deform_net = DeformNetwork (networks/sk_gs.py:209-315) as the shipped configs build it (exps/default.yaml:4-11,31:

@@ -250,7 +250,7 @@ int skgs_rasterize_backward(const skgs_raster_inputs* in, const skgs_raster_buff
         return 1;
     }
     if (const skgs_sp_skinning_job* sj0 = gr->sp_skinning_job)  // (empty lists: the superpoint gradients come out zero)
-      return sp_skinning_check(*sj0) || launch_sp_skinning_rest(*sj0, (hipStream_t) stream);
+      return sp_skinning_check(*sj0) || (!sp_fix_job(*sj0) && launch_sp_skinning_rest(*sj0, (hipStream_t) stream));
     return 0;
   }
   SKGS_REQUIRE(radii && out_opacity, "radii / out_opacity are required");
@@ -298,7 +298,7 @@ int skgs_rasterize_backward(const skgs_raster_inputs* in, const skgs_raster_buff
           gr->workspace, s))
     return 1;
   if (launch_preprocess_backward(*in, g, radii, *gr, s)) return 1;
-  if (sj) return launch_sp_skinning_rest(*sj, s);
+  if (sj) return sp_fix_job(*sj) ? 0 : launch_sp_skinning_rest(*sj, s);  // (stage sp_fix: the per-Gaussian launch was all of it)
   if (oj) return launch_offset_scale_grad_finalize(in->P, *oj, s);
   return dj ? launch_deform_backward_finalize(*dj->in, dj->workspace, dj->g_bone_T, dj->g_bone_drot, dj->g_bone_dscale, s) : 0;
 }

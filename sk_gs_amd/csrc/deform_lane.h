@@ -364,6 +364,7 @@ struct SpRowsArgs {
   int logits;
   float *g_weights, *g_xyz, *g_log_scale, *g_rot, *g_opacity_logit, *g_feature, *U, *V;
   const float* g_weights_extra;
+  int image_off;  // skgs_sp_skinning_job.image_to_deform_off: the image's cotangent stops at the Gaussian's own gradients
 };
 // the arguments from the public job (U and V are the first two pieces of its workspace: sp_backward.hip carves the same way)
 inline SpRowsArgs sp_rows_args(const skgs_sp_skinning_job& j) {
@@ -374,35 +375,36 @@ inline SpRowsArgs sp_rows_args(const skgs_sp_skinning_job& j) {
   float* V       = reinterpret_cast<float*>(wsp + align256(P * SP_UROW * 4));
   return SpRowsArgs{in->K, in->M, (int) in->largest, in->points, in->weights, in->indices, j.nn_dist, in->bone_T, in->bone_drot, in->bone_dscale,
       in->log_scale, in->rot, in->opacity_logit, j.feature, j.sp_feature, j.sp_radius_raw, j.sp_weight_raw, j.temperature,
-      (int) j.logit_weighting, j.g_weights, j.g_xyz, j.g_log_scale, j.g_rot, j.g_opacity_logit, j.g_feature, U, V, j.g_weights_extra};
+      (int) j.logit_weighting, j.g_weights, j.g_xyz, j.g_log_scale, j.g_rot, j.g_opacity_logit, j.g_feature, U, V, j.g_weights_extra,
+      j.image_to_deform_off ? 1 : 0};
 }
 inline size_t sp_rows_lds_bytes(int M) { return (size_t) M * BONE_F * 4; }
-// s_bones: [M][BONE_F] staged by the caller (load_bone), n: the lane's Gaussian (< P)
-template <int F>
-__device__ __forceinline__ void sp_rows_lane(const SpRowsArgs& ja, const float* s_bones, int n, const float (&g_dx_in)[3],
-    const float (&g_ds_in)[3], float4 gr4_in, float go_in) {
-  const float p[3] = {ja.points[3 * n], ja.points[3 * n + 1], ja.points[3 * n + 2]};
-  int jj[SP_MAXK];
-  float ww[SP_MAXK];
+// the lane's K neighbours (ids, weights)
+__device__ __forceinline__ void sp_rows_neighbours(const SpRowsArgs& ja, int n, int (&jj)[SP_MAXK], float (&ww)[SP_MAXK]) {
 #pragma unroll
   for (int k = 0; k < SP_MAXK; ++k) {
     jj[k] = k < ja.K ? (int) ja.indices[(size_t) n * ja.K + k] : 0;
     ww[k] = k < ja.K ? ja.weights[(size_t) n * ja.K + k] : 0.f;
   }
-  // ---- the Gaussian's own gradients (deform.hip::deform_backward_kernel, same expressions)
+}
+// ---- the Gaussian's own gradients (deform.hip::deform_backward_kernel, same expressions): g_xyz, g_log_scale, g_rot,
+// g_opacity_logit of Gaussian n are WRITTEN; g_v = d loss / d (rot + sr) is returned for the weights' gradient.  The one input
+// from the deform is sr = sum_k w_k d_rot[j_k]: `drot(j)` = superpoint j's d_rot row (from the LDS bone table in stage sp, in
+// place in stage sp_fix -- the same four values either way, so the same bits)
+template <class Drot>
+__device__ __forceinline__ void sp_gaussian_grads(const SpRowsArgs& ja, int n, const int (&jj)[SP_MAXK], const float (&ww)[SP_MAXK],
+    Drot drot, const float (&g_dx)[3], const float (&g_ds)[3], float4 gr4, float go, float (&g_v)[4]) {
   float sr[4] = {0, 0, 0, 0};
 #pragma unroll
   for (int k = 0; k < SP_MAXK; ++k)
     if (k < ja.K) {
-      const float* b = s_bones + jj[k] * BONE_F;
-      sr[0] += b[7] * ww[k], sr[1] += b[8] * ww[k], sr[2] += b[9] * ww[k], sr[3] += b[10] * ww[k];
+      const float4 b = drot(jj[k]);
+      sr[0] += b.x * ww[k], sr[1] += b.y * ww[k], sr[2] += b.z * ww[k], sr[3] += b.w * ww[k];
     }
   const float4 r4  = reinterpret_cast<const float4*>(ja.rot)[n];
-  const float4 gr4 = gr4_in;
   const float v[4]  = {r4.x + sr[0], r4.y + sr[1], r4.z + sr[2], r4.w + sr[3]};
   const float gr[4] = {gr4.x, gr4.y, gr4.z, gr4.w};
   const float nv    = sqrtf(v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3]);
-  float g_v[4];
   if (nv > 1e-12f) {
     const float u[4] = {v[0] / nv, v[1] / nv, v[2] / nv, v[3] / nv};
     const float dot  = u[0] * gr[0] + u[1] * gr[1] + u[2] * gr[2] + u[3] * gr[3];
@@ -412,35 +414,69 @@ __device__ __forceinline__ void sp_rows_lane(const SpRowsArgs& ja, const float* 
 #pragma unroll
     for (int c = 0; c < 4; ++c) g_v[c] = gr[c] / 1e-12f;
   }
-  const float g_dx[3] = {g_dx_in[0], g_dx_in[1], g_dx_in[2]};
-  const float g_ds[3] = {g_ds_in[0], g_ds_in[1], g_ds_in[2]};
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     ja.g_xyz[3 * n + c]       = g_dx[c];
     ja.g_log_scale[3 * n + c] = g_ds[c] * expf(ja.log_scale[3 * n + c]);
   }
   reinterpret_cast<float4*>(ja.g_rot)[n] = make_float4(g_v[0], g_v[1], g_v[2], g_v[3]);
-  const float sg     = 1.0f / (1.0f + expf(-ja.opacity_logit[n]));
-  ja.g_opacity_logit[n] = go_in * sg * (1.0f - sg);
+  const float sg        = 1.0f / (1.0f + expf(-ja.opacity_logit[n]));
+  ja.g_opacity_logit[n] = go * sg * (1.0f - sg);
+}
+// stage sp_fix (networks/sk_gs.py:1174-1178: d_xyz, d_rotation, d_scaling detached): the image's cotangent ends at the Gaussian's
+// own gradients.  The d_rot rows of the K neighbours are read in place (16 B each; the [M,4] table is L2-resident): no LDS.
+__device__ __forceinline__ void sp_fix_lane(const SpRowsArgs& ja, int n, const float (&g_dx)[3], const float (&g_ds)[3], float4 gr4,
+    float go) {
+  int jj[SP_MAXK];
+  float ww[SP_MAXK];
+  sp_rows_neighbours(ja, n, jj, ww);
+  const float4* drot = reinterpret_cast<const float4*>(ja.bone_drot);
+  float g_v[4];
+  sp_gaussian_grads(ja, n, jj, ww, [&](int j) { return drot[j]; }, g_dx, g_ds, gr4, go, g_v);
+}
+// s_bones: [M][BONE_F] staged by the caller (load_bone), n: the lane's Gaussian (< P).  ja.image_off (stage sp_fix with a cotangent
+// on the weights): the image's g_dx / g_v / g_ds stay out of the payload U and of g_weights -- only g_weights_extra enters them
+template <int F>
+__device__ __forceinline__ void sp_rows_lane(const SpRowsArgs& ja, const float* s_bones, int n, const float (&g_dx_in)[3],
+    const float (&g_ds_in)[3], float4 gr4_in, float go_in) {
+  const float p[3] = {ja.points[3 * n], ja.points[3 * n + 1], ja.points[3 * n + 2]};
+  int jj[SP_MAXK];
+  float ww[SP_MAXK];
+  sp_rows_neighbours(ja, n, jj, ww);
+  float g_v[4];
+  sp_gaussian_grads(ja, n, jj, ww, [&](int j) {
+        const float* b = s_bones + j * BONE_F;
+        return make_float4(b[7], b[8], b[9], b[10]);
+      }, g_dx_in, g_ds_in, gr4_in, go_in, g_v);
+  const float g_dx[3] = {g_dx_in[0], g_dx_in[1], g_dx_in[2]};
+  const float g_ds[3] = {g_ds_in[0], g_ds_in[1], g_ds_in[2]};
   float* un = ja.U + (size_t) n * SP_UROW;
-  reinterpret_cast<float4*>(un)[0] = make_float4(g_dx[0], g_dx[1], g_dx[2], g_v[0]);
-  reinterpret_cast<float4*>(un)[1] = make_float4(g_v[1], g_v[2], g_v[3], g_ds[0]);
-  reinterpret_cast<float4*>(un)[2] = make_float4(g_ds[1], g_ds[2], 0.f, 0.f);
+  if (ja.image_off) {
+    const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+    reinterpret_cast<float4*>(un)[0] = z, reinterpret_cast<float4*>(un)[1] = z, reinterpret_cast<float4*>(un)[2] = z;
+  } else {
+    reinterpret_cast<float4*>(un)[0] = make_float4(g_dx[0], g_dx[1], g_dx[2], g_v[0]);
+    reinterpret_cast<float4*>(un)[1] = make_float4(g_v[1], g_v[2], g_v[3], g_ds[0]);
+    reinterpret_cast<float4*>(un)[2] = make_float4(g_ds[1], g_ds[2], 0.f, 0.f);
+  }
   // ---- g_weights[k] = g_dx . (T_j p) + g_v . d_rot_j + g_ds . d_scale_j
   float gw[SP_MAXK];
 #pragma unroll
   for (int k = 0; k < SP_MAXK; ++k) {
     gw[k] = 0.f;
     if (k < ja.K) {
-      const float* b = s_bones + jj[k] * BONE_F;
-      float y[3];
-      se3_act(b, p, y);
-      float a = g_dx[0] * y[0] + g_dx[1] * y[1] + g_dx[2] * y[2];
-      if (ja.largest) a = 0.f;  // the position follows ONE bone: the weights reach the loss through the rotation / scale blend only
+      float a = 0.f;
+      if (!ja.image_off) {
+        const float* b = s_bones + jj[k] * BONE_F;
+        float y[3];
+        se3_act(b, p, y);
+        a = g_dx[0] * y[0] + g_dx[1] * y[1] + g_dx[2] * y[2];
+        if (ja.largest) a = 0.f;  // the position follows ONE bone: the weights reach the loss through the rotation / scale blend only
 #pragma unroll
-      for (int c = 0; c < 4; ++c) a += g_v[c] * b[7 + c];
+        for (int c = 0; c < 4; ++c) a += g_v[c] * b[7 + c];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) a += g_ds[c] * b[11 + c];
+        for (int c = 0; c < 3; ++c) a += g_ds[c] * b[11 + c];
+      }
       if (ja.g_weights_extra) a += ja.g_weights_extra[(size_t) n * ja.K + k];  // (a cotangent on the weights from outside the skinning)
       gw[k] = a;
       if (ja.g_weights) ja.g_weights[(size_t) n * ja.K + k] = a;

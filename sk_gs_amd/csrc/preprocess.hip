@@ -742,7 +742,9 @@ static_assert(PRE_BWD_THREADS == DEFORM_BWD_THREADS, "the deform backward job ru
 // JOB 0: none; 1 (DBJ): that; 2 / 3: the superpoint stage's ROWS pass (skgs_raster_grads.sp_skinning_job, sp_rows_lane<8 / 0>
 // of deform_lane.h = the body of sp_backward_rows_kernel) with its bone table in the same LDS; 4: stages init_fix / init
 // (skgs_raster_grads.offset_job): g_xyz = g_d_xyz = dL/dmean, normalize / sigmoid backward, the workgroup's partial of
-// sum(dL/dscale * scale) for the log-scale mean's backward (offset_scale_grad_finalize_kernel).
+// sum(dL/dscale * scale) for the log-scale mean's backward (offset_scale_grad_finalize_kernel); 5: stage sp_fix
+// (skgs_sp_skinning_job.image_to_deform_off without g_weights_extra: sp_fix_lane of deform_lane.h, the Gaussian's own four gradients
+// only -- no bone table in LDS, no payload, no g_weights; one instance, F plays no part in it).
 struct OffsetBwdArgs {
   int stride, per_row;
   const float *rot, *opacity_logit;
@@ -1159,6 +1161,9 @@ __global__ void __launch_bounds__(PRE_BWD_THREADS) preprocess_backward_kernel(in
     __syncthreads();
     if (idx < P) sp_rows_lane<(JOB == 2 ? 8 : 0)>(srj, s_sh, idx, dj_gm, dj_gs, dj_gr, dj_go);
   }
+  if constexpr (JOB == 5) {
+    if (idx < P) sp_fix_lane(srj, idx, dj_gm, dj_gs, dj_gr, dj_go);
+  }
 }
 
 // dL/dsh of `n_views` views from their factors (sh_backward): row i of Gaussian p = sum_v basis_i(dir_v) * g_v, views
@@ -1389,7 +1394,7 @@ int launch_preprocess_backward(const skgs_raster_inputs& in, GeomView g, const i
   SpRowsArgs srj{};
   if (const skgs_sp_skinning_job* j = gr.sp_skinning_job) {  // (checked by skgs_rasterize_backward)
     srj = sp_rows_args(*j);
-    lds = std::max(lds, sp_rows_lds_bytes(j->in->M));
+    if (!sp_fix_job(*j)) lds = std::max(lds, sp_rows_lds_bytes(j->in->M));  // (the fix job needs what the SH rows need)
   }
   OffsetBwdArgs obj{};
   if (const skgs_offset_deform_job* j = gr.offset_job) {  // (checked by skgs_rasterize_backward)
@@ -1404,7 +1409,8 @@ int launch_preprocess_backward(const skgs_raster_inputs& in, GeomView g, const i
       gr.dL_dopacity, gr.dL_dmeans3D, gr.dL_dcov3D, gr.dL_dsh, gr.dL_dsh_rest, gr.dL_dscales, gr.dL_drotations,           \
       gr.dL_dextras, gr.dL_dsh_factors, in.tanfov_device, in.live_count, gr.stat_xyz_gradient_accum, gr.stat_denom,        \
       gr.stat_max_radii2D, (gr.stat_grad_multiplier != 0.f ? gr.stat_grad_multiplier : 1.0f), dbj, srj, obj
-  const int job = gr.deform_backward_job ? 1 : gr.sp_skinning_job ? (gr.sp_skinning_job->F == 8 ? 2 : 3) : gr.offset_job ? 4 : 0;
+  const skgs_sp_skinning_job* sj = gr.sp_skinning_job;
+  const int job = gr.deform_backward_job ? 1 : sj ? (sp_fix_job(*sj) ? 5 : sj->F == 8 ? 2 : 3) : gr.offset_job ? 4 : 0;
 #define SKGS_PB(JOB_)                                                                                  \
   if (in.colmap)                                                                                       \
     hipLaunchKernelGGL((preprocess_backward_kernel<true, JOB_>), grid, block, lds, s, SKGS_PB_ARGS);   \
@@ -1415,6 +1421,7 @@ int launch_preprocess_backward(const skgs_raster_inputs& in, GeomView g, const i
     case 2: SKGS_PB(2); break;
     case 3: SKGS_PB(3); break;
     case 4: SKGS_PB(4); break;
+    case 5: SKGS_PB(5); break;
     default: SKGS_PB(0); break;
   }
 #undef SKGS_PB

@@ -479,6 +479,8 @@ int launch_knn_lbs_weights(int P, int M, int K, const float* points, const float
     float* out_weights, hipStream_t s);
 int sp_skinning_check(const skgs_sp_skinning_job& j);                       // sp_backward.hip
 int launch_sp_skinning_rest(const skgs_sp_skinning_job& j, hipStream_t s);  // bones + finalize
+// stage sp_fix without a cotangent on the weights: the Gaussian's own gradients only (no payload, no bones / finalize launches)
+inline bool sp_fix_job(const skgs_sp_skinning_job& j) { return j.image_to_deform_off != 0 && j.g_weights_extra == nullptr; }
 int launch_deform_backward_finalize(const skgs_deform_inputs& in, void* workspace, float* g_bone_T, float* g_bone_drot,
     float* g_bone_dscale, hipStream_t s);
 int deform_backward_job_max_bones();

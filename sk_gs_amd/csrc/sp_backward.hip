@@ -50,6 +50,16 @@ __global__ void __launch_bounds__(SB_THREADS) sp_backward_rows_kernel(int P, SpR
   sp_rows_lane<F>(ja, s_bones, n, g_dx, g_ds, reinterpret_cast<const float4*>(g_rotations)[n], g_opacity[n]);
 }
 
+// stage sp_fix without a cotangent on the weights (sp_fix_job): the Gaussian's own gradients, nothing in LDS
+__global__ void __launch_bounds__(SB_THREADS) sp_backward_fix_kernel(int P, SpRowsArgs ja, const float* __restrict__ g_means,
+    const float* __restrict__ g_scales, const float* __restrict__ g_rotations, const float* __restrict__ g_opacity) {
+  const int n = blockIdx.x * SB_THREADS + threadIdx.x;
+  if (n >= P) return;
+  const float g_dx[3] = {g_means[3 * n], g_means[3 * n + 1], g_means[3 * n + 2]};
+  const float g_ds[3] = {g_scales[3 * n], g_scales[3 * n + 1], g_scales[3 * n + 2]};
+  sp_fix_lane(ja, n, g_dx, g_ds, reinterpret_cast<const float4*>(g_rotations)[n], g_opacity[n]);
+}
+
 // ------------------------------------------------------------------------------------------------------------ bones
 template <int F>
 __global__ void __launch_bounds__(SB_THREADS) sp_backward_bones_kernel(int K, int M, int cap, const uint32_t* __restrict__ counts,
@@ -236,6 +246,33 @@ extern "C" {
 size_t skgs_sp_pairs_bytes(int32_t P, int32_t M, int32_t K) { return (P > 0 && M > 0 && K > 0) ? sp_pairs_bytes(P, M, K) : 0; }
 size_t skgs_sp_skinning_backward_workspace_bytes(int32_t P, int32_t M, int32_t K) { return sp_skinning_workspace_bytes(P, M, K); }
 
+int skgs_sp_skinning_backward_job(const skgs_sp_skinning_job* job, const float* g_means, const float* g_scales, const float* g_rotations,
+    const float* g_opacity, skgs_stream_t stream) {
+  SKGS_REQUIRE(job != nullptr, "sp_skinning_backward: job is NULL");
+  const skgs_sp_skinning_job& j = *job;
+  if (sp_skinning_check(j)) return 1;
+  const skgs_deform_inputs* in = j.in;
+  const int P = in->P, F = j.F;
+  SKGS_REQUIRE(P == 0 || (g_means && g_scales && g_rotations && g_opacity), "sp_skinning_backward: NULL argument");
+  hipStream_t s = (hipStream_t) stream;
+  ProfScope prof(K_DEFORM_BWD, s);
+  const bool fix = sp_fix_job(j);
+  if (P > 0) {
+    const SpRowsArgs ra = sp_rows_args(j);
+    const dim3 grid((P + SB_THREADS - 1) / SB_THREADS), block(SB_THREADS);
+    if (fix)
+      hipLaunchKernelGGL(sp_backward_fix_kernel, grid, block, 0, s, P, ra, g_means, g_scales, g_rotations, g_opacity);
+    else if (F == 8)
+      hipLaunchKernelGGL((sp_backward_rows_kernel<8>), grid, block, sp_rows_lds_bytes(in->M), s, P, ra, g_means, g_scales,
+          g_rotations, g_opacity);
+    else
+      hipLaunchKernelGGL((sp_backward_rows_kernel<0>), grid, block, sp_rows_lds_bytes(in->M), s, P, ra, g_means, g_scales,
+          g_rotations, g_opacity);
+    SKGS_CHECK_HIP(hipGetLastError());
+  }
+  return fix ? 0 : sp_skinning_rest_launches(j, s);
+}
+
 int skgs_sp_skinning_backward(const skgs_deform_inputs* in, int32_t F, const float* feature, const float* sp_feature,
     const float* sp_radius_raw, const float* sp_weight_raw, float temperature, int32_t logit_weighting, const float* nn_dist,
     const float* g_means, const float* g_scales, const float* g_rotations, const float* g_opacity, float* g_weights, float* g_xyz,
@@ -244,24 +281,8 @@ int skgs_sp_skinning_backward(const skgs_deform_inputs* in, int32_t F, const flo
     void* workspace, size_t workspace_bytes, skgs_stream_t stream) {
   const skgs_sp_skinning_job j{in, F, feature, sp_feature, sp_radius_raw, sp_weight_raw, temperature, logit_weighting, nn_dist,
       g_weights, g_xyz, g_log_scale, g_rot, g_opacity_logit, g_feature, g_bone_T, g_bone_drot, g_bone_dscale, g_sp_feature, g_sp_radius,
-      g_sp_weight, pairs, pairs_bytes, workspace, workspace_bytes};
-  if (sp_skinning_check(j)) return 1;
-  const int P = in->P;
-  SKGS_REQUIRE(P == 0 || (g_means && g_scales && g_rotations && g_opacity), "sp_skinning_backward: NULL argument");
-  hipStream_t s = (hipStream_t) stream;
-  ProfScope prof(K_DEFORM_BWD, s);
-  if (P > 0) {
-    const SpRowsArgs ra = sp_rows_args(j);
-    const dim3 grid((P + SB_THREADS - 1) / SB_THREADS), block(SB_THREADS);
-    if (F == 8)
-      hipLaunchKernelGGL((sp_backward_rows_kernel<8>), grid, block, sp_rows_lds_bytes(in->M), s, P, ra, g_means, g_scales,
-          g_rotations, g_opacity);
-    else
-      hipLaunchKernelGGL((sp_backward_rows_kernel<0>), grid, block, sp_rows_lds_bytes(in->M), s, P, ra, g_means, g_scales,
-          g_rotations, g_opacity);
-    SKGS_CHECK_HIP(hipGetLastError());
-  }
-  return sp_skinning_rest_launches(j, s);
+      g_sp_weight, pairs, pairs_bytes, workspace, workspace_bytes, nullptr, 0};
+  return skgs_sp_skinning_backward_job(&j, g_means, g_scales, g_rotations, g_opacity, stream);
 }
 
 }  // extern "C"

@@ -23,7 +23,7 @@ bone-moment finalize | skeleton backward) behind those two methods, on the model
   copy slower.
 
 Conditions of the fast path (anything else runs the reference's own ``render``; ``calls`` counts both and ``why_not`` keeps the last
-reason): stage ``sk``, ``sp``, ``init_fix`` or ``init``; training with grad enabled; ONE view; ``t`` / ``time_id`` / ``info`` tensors on the HIP device; no ``hook``
+reason): stage ``sk``, ``sp``, ``sp_fix``, ``init_fix`` or ``init``; training with grad enabled; ONE view; ``t`` / ``time_id`` / ``info`` tensors on the HIP device; no ``hook``
 (other keywords are ignored, as the reference's ``render`` ignores them); ``use_official_gaussians_render`` (the shipped configs), no
 ``convert_SHs_python`` / ``compute_cov3D``; a background of <= 3 values.  Stage ``sk``: the skeleton is initialised; ``LBS_method == 'W'``
 with ``sp_W`` [P, M] over the M <= 48 joints, ``num_knn`` <= 8; quaternion rotations, no ``sk_feature``; a ``SimpleDeformationNetwork`` the
@@ -35,6 +35,9 @@ of the node too -- the shipped ``sparse`` / ``smooth`` regularisers and the join
 cotangents enter the backward half (``skgs_sp_skinning_job.g_weights_extra``; ``g_bone_T`` before the network's backward).  Stages
 ``init_fix`` / ``init`` (``init_stage.FusedInitStep``): P >= 1, an ``sp_deform_net`` the P-row kernels cover with ``is_blender=True``, no positive
 ``p_arap_ct_init`` weight; the dict holds ``images``, ``viewspace_points``, ``radii``, ``points``, ``stage``; a refusal names the stage.
+Stage ``sp_fix`` (sk_gs.py:1174-1178: stage sp with the network's offsets detached): the conditions of sp and stage sp's route itself (same
+forward graph; ``FusedSuperpointStep.fix`` selects its two backward graphs, in which the image's cotangent ends at the six Gaussian tensors and
+only the parameters a cotangent reaches get a ``.grad``).  Building a route drops the model's routes of the stages the schedule has left.
 
 The forward half and the backward half are ONE hipGraph replay each (``SKGS_REF_FUSED_GRAPHS=0``: the same launches issued one by one);
 per call the host still issues the slot fill, the target's layout copy and the two loss launches.  Nothing blocks on the device per
@@ -54,7 +57,8 @@ import weakref
 import torch
 
 calls = {'render_fused': 0, 'render_reference': 0, 'image_terms_fused': 0, 'image_terms_reference': 0, 'backward_direct': 0,
-         'backward_cotangent': 0, 'foreign_grads_added': 0, 'routes_built': 0, 'capacity_grown': 0, 'capacity_retuned': 0, 'backward_extras': 0}
+         'backward_cotangent': 0, 'foreign_grads_added': 0, 'routes_built': 0, 'capacity_grown': 0, 'capacity_retuned': 0, 'backward_extras': 0,
+         'routes_released': 0}
 why_not = {'render': None, 'terms': None}
 _routes = weakref.WeakKeyDictionary()     # reference model -> FusedReferenceRoute | str (the reason there is none)
 CHECK_EVERY = 64
@@ -349,6 +353,9 @@ class FusedReferenceRoute:
         self.serial, self._fwd, self._terms, self._bg_key, self._spare = 0, None, None, None, None
         self._seen_events = 0
         self._attach = [(p, g, (p is net.last_weight or p is net.last_bias)) for p, g in self.grads.items()]
+        self.fix = False
+        if stage == 'sp':   # stage sp_fix (sk_gs.py:1174-1178): the attach list of each backward -- what the reference gives a gradient
+            self._attach_fix = self._fix_attach_lists()
         self._tiles = None
         if stage == 'sp':   # cotangents the reference's loss puts on outputs['_knn_w'] / outputs['_spT'] (sparse, smooth, joint: sk_gs.py:1555-1574)
             self.gw_extra = torch.zeros((self.view.P, self.view.K), dtype=torch.float32, device=dev)
@@ -364,6 +371,43 @@ class FusedReferenceRoute:
         self.use_graphs = os.environ.get('SKGS_REF_FUSED_GRAPHS', '1') != '0'
         calls['routes_built'] += 1
         _freeze_collector_once()
+
+    def _fix_attach_lists(self):
+        """stage sp_fix: {(cotangent on _knn_w, cotangent on _spT): attach list}.  The image reaches the six Gaussian tensors only; the
+        weights reach the weighting's parameters; the transforms (spT = (d_xyz, d_rotation), sk_gs.py:830-836) reach the network but its
+        scaling head (and local_rotation with sep_rot), and sp_points through the re-centring of LBS_c.  A parameter the reference gives
+        no gradient keeps ``.grad = None``: with zeros attached torch's Adam would move it on its old moments."""
+        v, net = self.view, self.shadow
+        six = {id(q) for q in (v._xyz, v._features_dc, v._features_rest, v._scaling, v._rotation, v._opacity)}
+        weighting = {id(q) for q in ([v.sp_W] if v.sp_W is not None else [v.hyper_feature, v.sp_hyper_feature, v._sp_radius, v._sp_weight])
+                     if q is not None}
+        off = {id(q) for m in [net.gaussian_scaling] + ([net.local_rotation] if net.sep_rot else []) for q in m.parameters()}
+        transforms = {id(q) for q in net.parameters() if id(q) not in off}
+        if v.warp_method == 'LBS_c':
+            transforms.add(id(v.sp_points))
+        lists = {}
+        for gw in (False, True):
+            for gT in (False, True):
+                want = six | (weighting if gw else set()) | (transforms if gT else set())
+                lists[(gw, gT)] = [e for e in self._attach if id(e[0]) in want]
+        return lists
+
+    def release(self):
+        """drop the graphs and every device buffer of the route (a stage the schedule has left: ``_route_for``); the object itself may
+        outlive this (``gc.freeze`` keeps cycles through it), its buffers do not"""
+        st = getattr(self, 'step', None)
+        if st is not None:      # (the step's own tensors too: a cycle through the step would keep them otherwise)
+            for k, val in list(vars(st).items()):
+                if torch.is_tensor(val):
+                    setattr(st, k, None)
+        self.graphs, self.step, self._fwd, self._terms, self._spare, self._keep = None, None, None, None, None, None
+        self.grads, self._attach, self._attach_fix, self._stores, self.vp, self.target, self.loss_ring = {}, [], {}, (), None, None, None
+        self.gw_extra = self.gT_extra = self.table = None
+        if self._tiles is not None:
+            ref = self.ref()
+            if ref is not None and getattr(getattr(ref, 'sp_W', None), '_skgs_logit_tiles', None) is self._tiles:
+                del ref.sp_W._skgs_logit_tiles
+            self._tiles = None
 
     # -------------------------------------------------------------------------------------------------------------------------
     @staticmethod
@@ -456,41 +500,58 @@ class FusedReferenceRoute:
         t = self.table.settings
         return (int(t.sh_degree), float(t.scale_modifier), self._bucket, self.step.binning.data_ptr())
 
-    def _capture(self):
+    # backward graphs: key -> (cotangents on _knn_w / _spT read from their persistent buffers, stage sp_fix)
+    _BACKWARDS = {'b': (False, False), 'bx': (True, False), 'fb': (False, True), 'fbx': (True, True)}
+
+    def _backward_keys(self):
+        """the backward graphs the current mode replays (stage sp: plain / with the extras; sp_fix: its own two)"""
+        if self.stage != 'sp':
+            return ('b',)
+        return ('fb', 'fbx') if self.fix else ('b', 'bx')
+
+    def _capture(self, more=False):
         """the forward half and the backward half as ONE hipGraph each (every pointer they bake in is persistent: parameters, the
         persistent gradients, the live slot, the background, the target and cotangent buffers); what still runs per call on the host:
         the slot fill, two replays, the loss launches.  Re-captured when the SH degree, the scale modifier or the binning buffer change;
-        a capture that fails leaves the eager launches in place."""
+        a capture that fails leaves the eager launches in place.  ``more``: add the backward graphs of the current mode to the
+        existing ones (the first sp_fix call after sp, or the other way round: sp_fix and sp share the route and its forward graph)."""
         from sk_gs_amd.train_step import GraphedSteps
         st = self.step
         saved = [(p, p.grad) for p, _, _ in self._attach]
         for p, g, _ in self._attach:
             p.grad = g
+        fix = self.fix
         try:
             def fwd(_):
                 self._fwd = st.forward(None, None)
 
             def bwd(k):
-                self._launch_backward(extras=(k == 'bx'))
+                extras, fix_k = self._BACKWARDS[k]
+                self._launch_backward(extras=extras, fix=fix_k)
             st.dL_dimage.zero_()      # (the warm-up execution of the backward half runs on it)
-            gs = GraphedSteps(lambda k: (fwd if k == 'f' else bwd)(k), warmup=1, collect_garbage=False, thread_local=True)
-            gs.capture('f')
-            gs.capture('b')
-            if self.stage == 'sp':    # the same with the cotangents on _knn_w / _spT read from their persistent buffers
-                gs.capture('bx')
+            if more:
+                gs = self.graphs
+            else:
+                gs = GraphedSteps(lambda k: (fwd if k == 'f' else bwd)(k), warmup=1, collect_garbage=False, thread_local=True)
+                gs.capture('f')
+            for k in self._backward_keys():
+                if k not in gs.graphs:
+                    gs.capture(k)
             self.graphs, self._graph_key = gs, self._graph_state()
         except Exception as e:   # noqa: BLE001  (no graph: the same launches, issued one by one)
             warnings.warn(f'fused reference route: hipGraph capture failed ({type(e).__name__}: {e}); using eager launches')
             self.graphs, self.use_graphs = None, False
         finally:
+            self.fix = fix
             for p, g in saved:
                 p.grad = g
 
-    def _launch_backward(self, extras=False):
+    def _launch_backward(self, extras=False, fix=False):
         st = self.step
         with torch.no_grad():
             if self.stage == 'sp':
                 st.g_weights_extra, st.g_bone_T_extra = (self.gw_extra, self.gT_extra) if extras else (None, None)
+                st.fix = fix
             st._zero_table_grads()
             st._raster_backward(self._fwd[0], self._fwd[1], None)
             st.backward_skinning(None)
@@ -558,8 +619,11 @@ class FusedReferenceRoute:
         self.set_background(background)
         if self.serial in self.RETUNE_AT or self.serial % self.RETUNE_EVERY == 0:
             self._retune()
+        self.fix = stage == 'sp_fix'
         if self.use_graphs and (self.graphs is None or self._graph_key != self._graph_state()):
             self._capture()
+        elif self.graphs is not None and any(k not in self.graphs.graphs for k in self._backward_keys()):
+            self._capture(more=True)
         st = self.step
         out = FusedOutputs(self)
         if self.stage == 'sk':
@@ -592,12 +656,12 @@ class FusedReferenceRoute:
         return out
 
     # -------------------------------------------------------------------------------------------------------------------------
-    def attach_grads(self):
+    def attach_grads(self, attach=None):
         """the parameters' ``.grad`` = the persistent tensors the kernels write (the reference sets them to None after every step,
         my_ext/framework.py:305); returns what has to be added afterwards: gradients another term accumulated before this node ran
-        (or ours from an earlier view that nobody cleared)"""
+        (or ours from an earlier view that nobody cleared).  ``attach``: the list of this backward (default: every parameter's)"""
         foreign = []
-        for p, g, store in self._attach:
+        for p, g, store in (self._attach if attach is None else attach):
             cur = p.grad
             if cur is None or store:
                 p.grad = g
@@ -629,12 +693,13 @@ class FusedReferenceRoute:
         else:
             calls['backward_direct'] += 1
         self._dimage_ready = False
-        foreign = self.attach_grads()
+        fix = self.fix
+        foreign = self.attach_grads(self._attach_fix[(g_w is not None, g_T is not None)] if fix else None)
         with torch.no_grad():
             if self.graphs is not None:
-                self.graphs.graphs['bx' if extras else 'b'].replay()
+                self.graphs.graphs[('f' if fix else '') + ('bx' if extras else 'b')].replay()
             else:
-                self._launch_backward(extras)
+                self._launch_backward(extras, fix)
             self.vp.grad = st.grad_means2D
             if foreign:
                 for ours, theirs in foreign:
@@ -783,8 +848,9 @@ class _FusedImageTerms(torch.autograd.Function):
 
 # ------------------------------------------------------------------------------------------------ recognising a fused image
 def route_of_model(model, stage='sk'):
-    """the route built for ``model`` in ``stage`` (None: none yet, or the conditions refused it -- ``why_not['render']``)"""
-    r = (_routes.get(model) or {}).get(stage)
+    """the route built for ``model`` in ``stage`` (None: none yet, or the conditions refused it -- ``why_not['render']``); sp_fix and sp
+    share one"""
+    r = (_routes.get(model) or {}).get(_route_key(stage))
     return None if (r is None or isinstance(r, tuple)) else r
 
 
@@ -848,11 +914,32 @@ def _size_of(info, cached):
 
 
 _INIT_STAGES = ('init_fix', 'init')
+# the reference's stages in schedule order (sk_gs.py:409); sp_fix and sp share a rank (and a route)
+_STAGE_ORDER = {'static': 0, 'init_fix': 1, 'init': 2, 'sp_fix': 3, 'sp': 3, 'sk_init': 4, 'sk_fix': 5, 'sk': 6}
+
+
+def _route_key(stage):
+    """stage sp_fix renders through stage sp's route (the same forward; its own backward graphs, sk_gs.py:1174-1178)"""
+    return 'sp' if stage == 'sp_fix' else stage
+
+
+def _release_earlier(per_stage, stage):
+    """a route is being built for ``stage``: the routes of the stages the schedule has left go (the init route alone holds ~1.7 GB at
+    P = 1e5); a stage rendered again later builds its route again"""
+    rank = _STAGE_ORDER.get(stage)
+    if rank is None:
+        return
+    for k in [k for k in per_stage if _STAGE_ORDER.get(k, rank) < rank]:
+        r = per_stage.pop(k)
+        if isinstance(r, FusedReferenceRoute):
+            r.release()
+            calls['routes_released'] += 1
 
 
 def _route_for(self, stage, t, info, background, time_id, scale_modifier, args, kwargs):
-    if stage not in ('sk', 'sp') + _INIT_STAGES:
-        return None, f'stage {stage!r} (the fused route covers sk, sp, init_fix and init)'
+    if stage not in ('sk', 'sp', 'sp_fix') + _INIT_STAGES:
+        return None, f'stage {stage!r} (the fused route covers sk, sp, sp_fix, init_fix and init)'
+    stage = _route_key(stage)
     if not (self.training and torch.is_grad_enabled()):
         return None, 'not training / grad disabled'
     if 'hook' in kwargs:      # (the only keyword the reference's render reads besides its named ones, sk_gs.py:1222-1223: it edits the
@@ -886,6 +973,7 @@ def _route_for(self, stage, t, info, background, time_id, scale_modifier, args, 
         if reason is not None:
             per_stage[stage] = (reason, _light_identity(self, stage))
             return None, reason
+        _release_earlier(per_stage, stage)
         cached = per_stage[stage] = FusedReferenceRoute(self, W, H, sh, scale_modifier, stage)
         cached.light = _light_identity(self, stage)
     cached.table.settings.sh_degree, cached.table.settings.scale_modifier = sh, float(scale_modifier)
@@ -935,7 +1023,7 @@ def render(self, *args, t=None, info, background=None, time_id=None, scale_modif
     stage = self.get_now_stage(stage)
     route, reason = _route_for(self, stage, t, info, background, time_id, scale_modifier, args, kwargs)
     if route is None:
-        if stage in _INIT_STAGES and not reason.startswith('stage '):
+        if stage in _INIT_STAGES + ('sp_fix',) and not reason.startswith('stage '):
             reason = f'stage {stage!r}: {reason}'
         why_not['render'] = reason
         calls['render_reference'] += 1

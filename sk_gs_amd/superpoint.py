@@ -554,6 +554,10 @@ class FusedSuperpointStep(FusedViewStep):
         # cotangents from OUTSIDE the step on the LBS weights [P,K] / the superpoint transforms [M,7] (the reference's loss reads
         # outputs['_knn_w'] and outputs['_spT']: sk_gs_amd/reference_fused.py): added inside the rows pass / before the network's backward
         self.g_weights_extra = self.g_bone_T_extra = None
+        # stage sp_fix (sk_gs.py:1174-1178: the network's offsets detached), chosen per call -- the forward is stage sp's: the image's
+        # cotangent reaches the six Gaussian tensors only (skgs_sp_skinning_job.image_to_deform_off); a cotangent on the weights or the
+        # transforms from outside still runs the weighting / network backward, on that cotangent alone
+        self.fix = False
         self.logit_mask = torch.zeros((P,), dtype=torch.int32, device=dev) if model.sp_W is not None else None
         self.sp_order = torch.empty((M,), dtype=torch.int32, device=dev)
         self.sp_rank = torch.empty((M,), dtype=torch.int32, device=dev)
@@ -646,6 +650,13 @@ class FusedSuperpointStep(FusedViewStep):
         the bones and finalize launches follow inside skgs_rasterize_backward.  SKGS_SEPARATE_DEFORM_BACKWARD=1: off"""
         if not self.deform_backward_in_preprocess:
             return None
+        j = self._skinning_job(d)
+        g.sp_skinning_job = C.cast(C.pointer(j), C.c_void_p)
+        self._rows_backward_done = True
+        return j
+
+    def _skinning_job(self, d):
+        """skgs_sp_skinning_job of this step (``d``: its deform inputs, kept alive by the caller)"""
         m = self.model
         gp = lambda t: None if t is None or t.grad is None else t.grad.data_ptr()  # noqa: E731
         pp = lambda t: None if t is None else t.data_ptr()  # noqa: E731
@@ -662,8 +673,7 @@ class FusedSuperpointStep(FusedViewStep):
         j.pairs, j.pairs_bytes = self.pairs.data_ptr(), self.pairs.numel()
         j.workspace, j.workspace_bytes = self.sb_ws.data_ptr(), self.sb_ws.numel()
         j.g_weights_extra = None if self.g_weights_extra is None else self.g_weights_extra.data_ptr()
-        g.sp_skinning_job = C.cast(C.pointer(j), C.c_void_p)
-        self._rows_backward_done = True
+        j.image_to_deform_off = 1 if self.fix else 0
         return j
 
     @torch.no_grad()
@@ -677,8 +687,11 @@ class FusedSuperpointStep(FusedViewStep):
         # skinning + weighting backward: rows | bones (the inverse lists of the forward) | finalize -- no atomics
         if self._rows_backward_done:  # (ran with the rasterizer's backward: _attach_backward_job; the flag stays until the next
             pass                       # backward_raster clears it -- see FusedViewStep.backward_skinning)
+        elif self.fix or self.g_weights_extra is not None:   # (the two fields the positional entry point has no parameter for)
+            j = self._skinning_job(d)
+            chk(lib.skgs_sp_skinning_backward_job(C.byref(j), _p(self.g_means), _p(self.g_scales), _p(self.g_rotations),
+                                                  _p(self.g_opacity), st))
         else:
-            assert self.g_weights_extra is None, 'a cotangent on the weights rides on the rows pass of the rasterizer backward (sp_skinning_job)'
             chk(lib.skgs_sp_skinning_backward(
                 C.byref(d), C.c_int32(self.F), _p(m.hyper_feature), _p(m.sp_hyper_feature), _p(m._sp_radius), _p(m._sp_weight),
                 C.c_float(m.lbs_temperature), C.c_int32(1 if logits else 0), _p(self.nn_dist), _p(self.g_means), _p(self.g_scales),
@@ -686,6 +699,8 @@ class FusedSuperpointStep(FusedViewStep):
                 _p(m._rotation.grad), _p(m._opacity.grad), None if logits else g(m.hyper_feature), _p(self.g_bone_T), _p(self.g_d_rot),
                 _p(self.g_d_scale), None if logits else g(m.sp_hyper_feature), g(m._sp_radius), g(m._sp_weight), _p(self.pairs),
                 C.c_size_t(self.pairs.numel()), _p(self.sb_ws), C.c_size_t(self.sb_ws.numel()), st))
+        if self.fix and self.g_weights_extra is None:  # stage sp_fix: the image's cotangent ended at the Gaussians' own gradients
+            return
         if logits and not self.sparse_logits:  # `W`: the dense [P,M] logit gradient (what autograd's gather backward builds)
             chk(lib.skgs_lbs_weights_backward(C.c_int32(P), C.c_int32(M), C.c_int32(K), _p(self.weights), _p(self.indices),
                                               _p(self.g_weights), _p(m.sp_W.grad), st))
