@@ -513,6 +513,25 @@ int skgs_weight_sparsity(int64_t n, const float* weights, float eps, float* grad
 int skgs_weight_smooth(int32_t P, int32_t K, int32_t G, const float* weights, const int64_t* neighbours, const int32_t* inverse_offsets,
     const int32_t* inverse_sources, float* grad, float* partials, skgs_stream_t stream);
 
+/* ---- the joint-discovery loss of stage `sp` (networks/sk_gs.py:1309-1336; `joint` / `joint_all`, exps/default.yaml:93-94) ----
+ * spT [M, 7] rows (t, q xyzw, NOT normalised; R = the polynomial of quaternion_to_Rt), joint_pos [M, M, 3], 2 <= M <= 1024.  Per pair
+ * jd[a, b] = |R_b p_ab + t_b - R_a p_ab - t_a| (inverse_branch = 0: canonical_time_id >= 0) or |R_b^-1 (R_a p_ab + t_a - t_b) - p_ab|
+ * (inverse_branch = 1), plus |R_b p_ab + t_b - R_a p_ba - t_a|; the diagonal is 0.  The forward writes jd [M, M], cost_out = cost_in *
+ * momentum + jd * one_minus_momentum (cost_out NULL: no EMA) and skgs_joint_loss_partials(M) fixed-order partial sums of jd.  The reduce
+ * launch (after the caller's tree update) writes out[0] = best = mean over the `edges` nodes a with parent[a] >= 0 of
+ * (jd[a, parent a] + jd[parent a, a]) / 2 and out[1] = all = mean(jd); parent: int32 [M], -1 for the root.
+ * The backward takes DEVICE cotangents grad_best / grad_all (NULL = 0) and writes every element of g_joint_pos [M, M, 3]; g_spT [M, 7]
+ * (NULL: none) needs skgs_joint_loss_backward_workspace_bytes(M).  No float atomics in either direction: bitwise reproducible. */
+int32_t skgs_joint_loss_partials(int32_t M);
+int skgs_joint_loss_forward(int32_t M, int32_t inverse_branch, const float* spT, const float* joint_pos, const float* cost_in, float momentum,
+    float one_minus_momentum, float* cost_out, float* jd, float* partials, skgs_stream_t stream);
+int skgs_joint_loss_reduce(int32_t M, int32_t edges, const int32_t* parent, const float* jd, const float* partials, float* out,
+    skgs_stream_t stream);
+size_t skgs_joint_loss_backward_workspace_bytes(int32_t M);
+int skgs_joint_loss_backward(int32_t M, int32_t inverse_branch, int32_t edges, const float* spT, const float* joint_pos, const int32_t* parent,
+    const float* grad_best, const float* grad_all, float* g_joint_pos, float* g_spT, void* workspace, size_t workspace_bytes,
+    skgs_stream_t stream);
+
 /* ---- the live view slot from the reference's per-view tensors (no host read-back) ----
  * Replaces the host side of `prepare_inputs` (networks/gaussian_splatting.py:247-300) for one view: the reference builds
  * GaussianRasterizationSettings from `info` with `math.tan(0.5 * FoV[b, 0])` and `info['Tw2v']` on the host -- a blocking

@@ -119,6 +119,8 @@ EXPORTED_SYMBOLS = [
     'skgs_knn_dist_weights_workspace_bytes', 'skgs_mark_visible', 'skgs_lbs_deform_forward',
     'skgs_lbs_deform_backward', 'skgs_lbs_deform_backward_workspace_bytes', 'skgs_knn_bones',
     'skgs_lbs_weights_forward', 'skgs_lbs_weights_backward', 'skgs_last_error', 'skgs_version',
+    'skgs_joint_loss_partials', 'skgs_joint_loss_forward', 'skgs_joint_loss_reduce', 'skgs_joint_loss_backward_workspace_bytes',
+    'skgs_joint_loss_backward',
 ]
 
 

@@ -130,12 +130,13 @@ def install_as_pytorch3d():
     return ops
 
 
-def install_reference_hooks(single_thread: bool = True, accelerate: bool = False):
+def install_reference_hooks(single_thread: bool = True, accelerate: bool = False, joint_loss: bool = False):
     """Everything an unmodified checkout of the reference needs from this package on an MI355X machine, in one call made BEFORE
     ``import my_ext`` / ``import networks`` / ``import train``: the compiled ops behind ``my_ext._C`` (``install_as_my_ext_C``), the
     shipped configs' rasterizer package (``install_as_diff_gaussian_rasterization``), and the two CUDA-only third-party packages of
     the deform (``install_as_lietorch``, ``install_as_pytorch3d``).  ``accelerate=True``: ``accelerate_reference()``'s fast paths are
-    applied as the reference's modules arrive (no second call).  INTEGRATION.md section 1."""
+    applied as the reference's modules arrive (no second call); ``joint_loss=True`` adds the opt-in joint-discovery loss
+    (``sk_gs_amd.joint_loss``).  INTEGRATION.md section 1."""
     install_as_my_ext_C(single_thread=single_thread)
     install_as_diff_gaussian_rasterization(single_thread=single_thread)
     install_as_lietorch()
@@ -145,12 +146,12 @@ def install_reference_hooks(single_thread: bool = True, accelerate: bool = False
         # hook): the two lines `import sk_gs_amd; sk_gs_amd.install_reference_hooks(accelerate=True)` in front of the reference's own
         # imports are then everything
         from sk_gs_amd import reference_accel
-        reference_accel.install_post_import_patcher()
+        reference_accel.install_post_import_patcher(**({'joint_loss': True} if joint_loss else {}))
     return ['my_ext._C._C', 'diff_gaussian_rasterization', 'lietorch', 'pytorch3d.ops']
 
 
 def accelerate_reference(ssim: bool = True, kinematic_chain: bool = True, networks: bool = True, lbs_weights: bool = True,
-                         adam: bool = True, swizzle: bool = True, fused_render: bool = True) -> list:
+                         adam: bool = True, swizzle: bool = True, fused_render: bool = True, joint_loss: bool = False) -> list:
     """AFTER the reference has been imported (``install_reference_hooks()`` before it): give methods of its classes a fast path --
     ``SSIM_Loss.forward`` (3.5 ms of depth-wise convolutions per image -> the fused loss kernels),
     ``SkeletonGaussianSplatting.kinematic`` (~60 Lie-group launches -> one bone-chain launch per direction),
@@ -164,10 +165,13 @@ def accelerate_reference(ssim: bool = True, kinematic_chain: bool = True, networ
     ``fused_render`` (round 6): ``SkeletonGaussianSplatting.render`` + ``ImageLoss.forward`` + ``SSIM_Loss.forward`` put the package's
     WHOLE fused per-view step (11 launches forward + backward, the trainer's own) behind the reference's iteration for stage ``sk`` on
     the model's own parameters -- ``sk_gs_amd.reference_fused``; calls outside its conditions run the reference's ``render`` and, inside
-    it, the per-method fast paths above."""
+    it, the per-method fast paths above.
+
+    ``joint_loss`` (opt-in): ``SkeletonGaussianSplatting.loss_joint_discovery`` (stage sp's ``joint`` / ``joint_all``) through the pair
+    kernels of ``sk_gs_amd.joint_loss`` and the module global ``networks.sk_gs.joint_discovery`` (the tree rebuild) on the host."""
     from sk_gs_amd import reference_accel
     return reference_accel.accelerate_reference(ssim=ssim, kinematic_chain=kinematic_chain, networks=networks, lbs_weights=lbs_weights, adam=adam,
-                                                swizzle=swizzle, fused_render=fused_render)
+                                                swizzle=swizzle, fused_render=fused_render, joint_loss=joint_loss)
 
 
 def install_as_diff_gaussian_rasterization(single_thread: bool = True):

@@ -660,7 +660,7 @@ def install_post_import_patcher(**kwargs):
 
 
 def accelerate_reference(ssim: bool = True, kinematic_chain: bool = True, networks: bool = True, lbs_weights: bool = True,
-                         adam: bool = True, swizzle: bool = True, strict: bool = True, fused_render: bool = True) -> list:
+                         adam: bool = True, swizzle: bool = True, strict: bool = True, fused_render: bool = True, joint_loss: bool = False) -> list:
     """Patch the methods on the reference's classes (the modules must be imported already; ``strict=False``: patch what IS imported,
     skip the rest -- what the post-import hook of ``install_reference_hooks(accelerate=True)`` calls as the modules arrive).  Returns what
     was patched."""
@@ -668,6 +668,7 @@ def accelerate_reference(ssim: bool = True, kinematic_chain: bool = True, networ
     if not strict:
         sk, ss = _fully_imported('networks.sk_gs'), _fully_imported('networks.losses.ssim')
         networks, kinematic_chain, lbs_weights, ssim = networks and sk, kinematic_chain and sk, lbs_weights and sk, ssim and ss
+        joint_loss = joint_loss and sk
         fused_render = fused_render and sk and ss and _fully_imported('networks.losses.image_loss')
     if fused_render:
         # the whole per-view step behind SkeletonGaussianSplatting.render + the two image terms (sk_gs_amd/reference_fused.py): render
@@ -745,6 +746,20 @@ def accelerate_reference(ssim: bool = True, kinematic_chain: bool = True, networ
             _originals['kinematic'] = mod.SkeletonGaussianSplatting.kinematic
             mod.SkeletonGaussianSplatting.kinematic = kinematic
         done.append('networks.sk_gs.SkeletonGaussianSplatting.kinematic')
+    if joint_loss:
+        # opt-in: stage sp's joint-discovery loss (sk_gs.py:1309-1336) and the tree rebuild it triggers, the module global
+        # `joint_discovery` that update_joint (:1245-1265) looks up at call time -- sk_gs_amd/joint_loss.py
+        from sk_gs_amd import joint_loss as jl
+        mod = sys.modules.get('networks.sk_gs')
+        if mod is None:
+            raise RuntimeError("accelerate_reference(): import the reference first (networks.sk_gs is not loaded)")
+        if 'joint_loss' not in _originals:
+            _originals['joint_loss'] = jl._originals['loss'] = mod.SkeletonGaussianSplatting.loss_joint_discovery
+            mod.SkeletonGaussianSplatting.loss_joint_discovery = jl.loss_joint_discovery
+        if 'joint_discovery' not in _originals:
+            _originals['joint_discovery'] = jl._originals['discovery'] = mod.joint_discovery
+            mod.joint_discovery = jl.joint_discovery
+        done += ['networks.sk_gs.SkeletonGaussianSplatting.loss_joint_discovery', 'networks.sk_gs.joint_discovery']
     return done
 
 
@@ -783,3 +798,8 @@ def restore_reference():
     if 'w_sparse' in _originals and 'networks.sk_gs' in sys.modules:
         sys.modules['networks.sk_gs'].SkeletonGaussianSplatting.loss_weight_sparsity = _originals.pop('w_sparse')
         sys.modules['networks.sk_gs'].SkeletonGaussianSplatting.loss_weight_smooth = _originals.pop('w_smooth')
+    if 'joint_loss' in _originals and 'networks.sk_gs' in sys.modules:
+        from sk_gs_amd import joint_loss as jl
+        sys.modules['networks.sk_gs'].SkeletonGaussianSplatting.loss_joint_discovery = _originals.pop('joint_loss')
+        sys.modules['networks.sk_gs'].joint_discovery = _originals.pop('joint_discovery')
+        jl._originals.clear()
