@@ -953,6 +953,21 @@ int skgs_densify_stats(int32_t P, const int32_t* radii, const float* grad_means2
  * to its three nearest other points.  points [P,3], mean_dist2 [P]. */
 int skgs_simple_knn(int32_t P, const float* points, float* mean_dist2, skgs_stream_t stream);
 
+/* ---- exact K nearest neighbours among 3-D points (csrc/point_knn.hip): the Gaussians' neighbour table of networks/sk_gs.py:1342-1355
+ * (`update_gs_knn`, P x P, K = gs_knn_num + 1 = 21) and `knn_points` over all Gaussians (sk_gs.py:1365) ----
+ * data [n_data,3], queries [n_query,3] (NULL: the data themselves, n_query = n_data), 1 <= K <= 32.  Distances are
+ * dx*dx + dy*dy + dz*dz in fp32, summed left to right without contraction; every row ascends by (distance, index), ties to the
+ * lower index -- bit-identical to a stable sort of the full distance matrix, duplicates included.  In a self query a point is its own
+ * neighbour at distance 0 (not necessarily column 0 when an exact duplicate has a lower index).  Columns beyond n_data get index -1
+ * and distance +inf.  out_idx [n_query,K]; out_dist2 (squared) / out_dist (Euclidean) [n_query,K], either may be NULL.  Rows with
+ * non-finite coordinates get unspecified neighbours.  n_data = 0 or n_query = 0: nothing is done.  Enqueues on `stream` only: no host
+ * synchronisation, allocation or read-back; the scratch (Morton keys, the sort's buffers, the Z-ordered copy, one box per 64 points)
+ * is the caller's `workspace` of skgs_point_knn_workspace_bytes(n_data, n_query) bytes (sized for the current device: the stream's), 16-byte aligned.  No float atomics: the same
+ * inputs give the same bits. */
+size_t skgs_point_knn_workspace_bytes(int32_t n_data, int32_t n_query);
+int skgs_point_knn(int32_t n_data, const float* data, int32_t n_query, const float* queries, int32_t K, int64_t* out_idx,
+    float* out_dist2, float* out_dist, void* workspace, size_t workspace_bytes, skgs_stream_t stream);
+
 /* ---- densification surgery in one launch (scope row (f)-4) ----
  * Replaces the per-tensor indexing / concatenation of change_optimizer, prune_points and densification_postfix
  * (networks/gaussian_splatting.py:515-587) over the per-Gaussian parameters and their Adam moments: for every tensor t of

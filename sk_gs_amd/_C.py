@@ -120,7 +120,7 @@ EXPORTED_SYMBOLS = [
     'skgs_lbs_deform_backward', 'skgs_lbs_deform_backward_workspace_bytes', 'skgs_knn_bones',
     'skgs_lbs_weights_forward', 'skgs_lbs_weights_backward', 'skgs_last_error', 'skgs_version',
     'skgs_joint_loss_partials', 'skgs_joint_loss_forward', 'skgs_joint_loss_reduce', 'skgs_joint_loss_backward_workspace_bytes',
-    'skgs_joint_loss_backward',
+    'skgs_joint_loss_backward', 'skgs_point_knn_workspace_bytes', 'skgs_point_knn',
 ]
 
 
@@ -814,6 +814,59 @@ def knn_bones(points: Tensor, joints: Tensor, K: int) -> Tuple[Tensor, Tensor]:
                                   C.c_void_p(_ptr(points)), C.c_void_p(joints.data_ptr()), C.c_void_p(_ptr(dist)),
                                   C.c_void_p(_ptr(idx)), _stream()))
     return dist, idx
+
+
+_point_knn_ws = {}   # (device index, n_data, n_query) -> scratch of skgs_point_knn (grows only: one tensor per device serves every smaller call)
+
+
+def _point_knn_workspace(lib, dev, n_data: int, n_query: int) -> Tensor:
+    key = (dev.index, n_data, n_query)
+    need = _point_knn_ws.get(key)
+    if need is None:
+        lib.skgs_point_knn_workspace_bytes.restype = C.c_size_t
+        need = _point_knn_ws[key] = int(lib.skgs_point_knn_workspace_bytes(C.c_int32(n_data), C.c_int32(n_query)))
+    ws = _point_knn_ws.get(dev.index)
+    if ws is None or ws.numel() < need:
+        ws = _point_knn_ws[dev.index] = torch.empty(need + need // 4, dtype=torch.uint8, device=dev)
+    return ws
+
+
+def point_knn(data: Tensor, queries: Optional[Tensor] = None, K: int = 1, want: str = 'dist2'):
+    """Exact K nearest rows of ``data [n,3]`` for every row of ``queries [m,3]`` (``None``: the data themselves; a point is then its
+    own neighbour at distance 0) -- ``skgs_point_knn`` (csrc/point_knn.hip): Z-order, one box per 64 points, pruned wave-wide scan.
+    ``1 <= K <= 32``; rows ascend by (distance, index), ties to the lower index; columns beyond ``n`` hold index -1, distance inf.
+    Returns ``(idx [m,K] int64, dist2)`` (``want='dist2'``, squared), ``(idx, dist)`` (``'dist'``, Euclidean) or ``(idx, dist2, dist)``
+    (``'both'``).  Enqueues on the current stream: no synchronisation, no host copy; the scratch is cached and grows only."""
+    if want not in ('dist2', 'dist', 'both'):
+        raise SkgsError(f"point_knn: want must be 'dist2', 'dist' or 'both' (got {want!r})")
+    lib = load_library()
+    _require_gpu(data, 'data')
+    dev = data.device
+    with _on_device(dev):
+        data = _f32c(data, dev)
+        if data.dim() != 2 or data.shape[1] != 3:
+            raise SkgsError('point_knn: data must have shape (n, 3)')
+        q = None
+        if queries is not None:
+            q = _f32c(queries, dev)
+            if q.dim() != 2 or q.shape[1] != 3:
+                raise SkgsError('point_knn: queries must have shape (m, 3)')
+        n, m = data.shape[0], (data.shape[0] if q is None else q.shape[0])
+        idx = torch.empty((m, K), dtype=torch.int64, device=dev)
+        d2 = torch.empty((m, K), dtype=torch.float32, device=dev) if want in ('dist2', 'both') else None
+        d1 = torch.empty((m, K), dtype=torch.float32, device=dev) if want in ('dist', 'both') else None
+        if n == 0 and m > 0:     # (the library does nothing for an empty cloud: the fill values of "fewer than K points")
+            idx.fill_(-1)
+            for t in (d2, d1):
+                if t is not None:
+                    t.fill_(float('inf'))
+        ws = _point_knn_workspace(lib, dev, n, m) if (n > 0 and m > 0) else None
+        _check(lib.skgs_point_knn(C.c_int32(n), C.c_void_p(_ptr(data)), C.c_int32(m), C.c_void_p(_ptr(q)), C.c_int32(K),
+                                  C.c_void_p(_ptr(idx)), C.c_void_p(_ptr(d2)), C.c_void_p(_ptr(d1)), C.c_void_p(_ptr(ws)),
+                                  C.c_size_t(0 if ws is None else ws.numel()), _stream()))
+    if want == 'both':
+        return idx, d2, d1
+    return idx, (d2 if want == 'dist2' else d1)
 
 
 def bone_chain_forward(sk_r_raw: Tensor, joints: Tensor, global_T: Optional[Tensor], topo: dict,

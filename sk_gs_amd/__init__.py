@@ -7,6 +7,7 @@ Layout (only what the path needs):
   renderer/gaussian_render  mirror of networks/renderer/gaussian_render.py
   diff_gaussian_rasterization  upstream-compatible front end (variant A of the boundary)
   deform.py / skeleton.py   lbs_deform autograd op, bone chain
+  pykdtree.py               stand-in for the CPU KD-tree package of `update_gs_knn` (the Gaussians' neighbour table: csrc/point_knn.hip)
   lietorch.py / pytorch3d_ops.py  stand-ins for the two CUDA-only packages networks/sk_gs.py imports (SE3 / SO3, knn_points): the
                             reference's deform runs UNMODIFIED on them, its skinning expression and search as launches of the library
   scene.py / model.py       synthetic scenes and the minimal skinned-Gaussian module used by tests and bench
@@ -130,24 +131,51 @@ def install_as_pytorch3d():
     return ops
 
 
+def install_as_pykdtree():
+    """``from pykdtree.kdtree import KDTree`` (networks/sk_gs.py:1349, ``update_gs_knn``: the Gaussians' 21-column neighbour table of
+    ``loss_weight_smooth``) resolves to ``sk_gs_amd.pykdtree``: an exact search with pykdtree's ``query`` contract -- one
+    ``skgs_point_knn`` call on a HIP device, a chunked brute force on a machine without one.  ``SKGS_PYKDTREE=0`` leaves ``sys.modules``
+    alone (a user who prefers an installed pykdtree); a real pykdtree that is already imported is never shadowed.  Returns the module
+    that ``pykdtree.kdtree`` now names, or None when nothing was planted."""
+    import os
+    import sys
+    import types
+    if os.environ.get('SKGS_PYKDTREE', '1') == '0':
+        return None
+    from sk_gs_amd import pykdtree as m
+    have = sys.modules.get('pykdtree')
+    if have is not None and not getattr(have, '_sk_gs_amd_stand_in', False):
+        return None  # a real pykdtree is already in use: it does the same job on the host
+    if have is None:
+        pkg = types.ModuleType('pykdtree')
+        pkg.__path__ = []
+        pkg._sk_gs_amd_stand_in = True
+        pkg.__version__ = '0.0.0+sk_gs_amd'
+        pkg.kdtree = m
+        sys.modules['pykdtree'] = pkg
+    sys.modules['pykdtree.kdtree'] = m
+    return m
+
+
 def install_reference_hooks(single_thread: bool = True, accelerate: bool = False, joint_loss: bool = False):
     """Everything an unmodified checkout of the reference needs from this package on an MI355X machine, in one call made BEFORE
     ``import my_ext`` / ``import networks`` / ``import train``: the compiled ops behind ``my_ext._C`` (``install_as_my_ext_C``), the
     shipped configs' rasterizer package (``install_as_diff_gaussian_rasterization``), and the two CUDA-only third-party packages of
-    the deform (``install_as_lietorch``, ``install_as_pytorch3d``).  ``accelerate=True``: ``accelerate_reference()``'s fast paths are
+    the deform (``install_as_lietorch``, ``install_as_pytorch3d``), and the CPU package of the neighbour table (``install_as_pykdtree``).  ``accelerate=True``: ``accelerate_reference()``'s fast paths are
     applied as the reference's modules arrive (no second call); ``joint_loss=True`` adds the opt-in joint-discovery loss
     (``sk_gs_amd.joint_loss``).  INTEGRATION.md section 1."""
     install_as_my_ext_C(single_thread=single_thread)
     install_as_diff_gaussian_rasterization(single_thread=single_thread)
     install_as_lietorch()
     install_as_pytorch3d()
+    kd = install_as_pykdtree()
     if accelerate:
         # ... and the fast paths of accelerate_reference() applied BY THEMSELVES as the reference's modules finish importing (a post-import
         # hook): the two lines `import sk_gs_amd; sk_gs_amd.install_reference_hooks(accelerate=True)` in front of the reference's own
         # imports are then everything
         from sk_gs_amd import reference_accel
         reference_accel.install_post_import_patcher(**({'joint_loss': True} if joint_loss else {}))
-    return ['my_ext._C._C', 'diff_gaussian_rasterization', 'lietorch', 'pytorch3d.ops']
+    return ['my_ext._C._C', 'diff_gaussian_rasterization', 'lietorch', 'pytorch3d.ops'] + (['pykdtree.kdtree'] if kd is not None else [])
 
 
 def accelerate_reference(ssim: bool = True, kinematic_chain: bool = True, networks: bool = True, lbs_weights: bool = True,
@@ -166,6 +194,11 @@ def accelerate_reference(ssim: bool = True, kinematic_chain: bool = True, networ
     WHOLE fused per-view step (11 launches forward + backward, the trainer's own) behind the reference's iteration for stage ``sk`` on
     the model's own parameters -- ``sk_gs_amd.reference_fused``; calls outside its conditions run the reference's ``render`` and, inside
     it, the per-method fast paths above.
+
+    With ``lbs_weights`` the two weight regularisers of stage ``sp`` are patched too, and with ``loss_weight_smooth`` the method it calls,
+    ``SkeletonGaussianSplatting.update_gs_knn`` (the Gaussians' neighbour table as one ``skgs_point_knn`` call on the device): that patch
+    rides with ``loss_weight_smooth`` -- it is not listed on its own in the returned names and is switched off with ``lbs_weights=False``;
+    ``reference_accel.restore_reference()`` undoes it with the rest.
 
     ``joint_loss`` (opt-in): ``SkeletonGaussianSplatting.loss_joint_discovery`` (stage sp's ``joint`` / ``joint_all``) through the pair
     kernels of ``sk_gs_amd.joint_loss`` and the module global ``networks.sk_gs.joint_discovery`` (the tree rebuild) on the host."""

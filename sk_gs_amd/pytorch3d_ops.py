@@ -16,8 +16,10 @@ same as csrc/deform.hip and the oracle); ``dists`` is differentiable w.r.t. p1 a
 
 On a HIP device the per-frame call shape (one cloud, no lengths, squared L2, K <= 16, D <= 16, fp32) is ONE launch of
 libskgs_hip.so: ``skgs_sp_lbs_weights_forward`` for superpoint-sized tables (60 < M <= 1024 in 3 or 3 + 8 dimensions: the
-wave-cooperative pruned scan of csrc/sp_knn.hip) and ``skgs_knn_bones`` otherwise -- no fallback when the library is missing.
-Everything else (CPU tensors, batches, lengths, L1, large K) runs as chunked pure torch.  The indices that call returns are typed
+wave-cooperative pruned scan of csrc/sp_knn.hip) and ``skgs_knn_bones`` otherwise -- no fallback when the library is missing.  A 3-D
+table of more than 1024 points with 16 < K <= 32, or of more than 4096 with K <= 16 (all Gaussians against themselves, sk_gs.py:1365, K = 21) is ``skgs_point_knn``
+(csrc/point_knn.hip: Z-order, one box per 64 points, exact pruned search; the same bits as the chunked torch path).
+Everything else (CPU tensors, batches, lengths, L1, K > 16 on small tables) runs as chunked pure torch.  The indices that call returns are typed
 (``NeighbourIndex``, a ``torch.Tensor`` subclass over the same int64 storage) so that the reference's own gathers of per-bone rows by
 them -- ``sk_d_rot[indices]``, ``kernel_radius[indices]`` ... -- get a backward (``skgs_index_add_rows``) that does not walk
 duplicates serially: torch's index backward is 7.5 ms per gather at 100k x 5 indices into 20 rows (``SKGS_KNN_TYPED_INDEX=0``: plain).
@@ -36,7 +38,17 @@ __all__ = ['knn_points', 'knn_gather', 'ball_query']
 
 _KNN = namedtuple('KNN', 'dists idx knn')
 _TYPED_INDEX = os.environ.get('SKGS_KNN_TYPED_INDEX', '1') != '0'
-hip_calls = {'knn_bones': 0, 'sp_search': 0, 'gather_backward': 0}  # counters (tests)
+# 3-D tables larger than this go to skgs_point_knn.  K > 16 had no kernel at all (chunked torch): every table beyond the superpoint
+# scan's 1024 rows.  K <= 16 has the plain P x M scan of skgs_knn_bones, written for bone-sized tables and still the shorter call for
+# a few thousand rows (no sort, no build): those calls keep it up to 4096 rows -- both give the same bits.
+_POINT_KNN_MIN, _POINT_KNN_MIN_SCAN = 1024, 4096
+
+
+def _to_point_knn(P2: int, D: int, K: int) -> bool:
+    return D == 3 and 1 <= K <= 32 and P2 > (_POINT_KNN_MIN if K > 16 else _POINT_KNN_MIN_SCAN)
+
+
+hip_calls = {'knn_bones': 0, 'sp_search': 0, 'gather_backward': 0, 'point_knn': 0}  # counters (tests)
 
 
 def _index_add_rows(index: Tensor, rows: Tensor, shape) -> Tensor:
@@ -146,10 +158,15 @@ class _KnnHip(torch.autograd.Function):
         with _C._on_device(dev):
             a, b = _C._f32c(p1, dev), _C._f32c(p2, dev)
             (P, D), M = a.shape, b.shape[0]
-            dist = torch.empty((P, K), dtype=torch.float32, device=dev)
-            idx = torch.empty((P, K), dtype=torch.int64, device=dev)
             ptr = lambda t: C.c_void_p(_C._ptr(t))  # noqa: E731
-            if 60 < M <= 1024 and D in (3, 11):
+            if not _to_point_knn(M, D, K):
+                dist = torch.empty((P, K), dtype=torch.float32, device=dev)
+                idx = torch.empty((P, K), dtype=torch.int64, device=dev)
+            if _to_point_knn(M, D, K):
+                # a table of Gaussian size (sk_gs.py:1365: all Gaussians against themselves, K = 21): the Z-ordered pruned search
+                idx, dist = _C.point_knn(b, None if (a is b or (a.data_ptr() == b.data_ptr() and a.shape == b.shape)) else a, K=K)
+                hip_calls['point_knn'] += 1
+            elif 60 < M <= 1024 and D in (3, 11):
                 F = D - 3
                 xyz, feat = (a, None) if F == 0 else (a[:, :3].contiguous(), a[:, 3:].contiguous())
                 sxyz, sfeat = (b, None) if F == 0 else (b[:, :3].contiguous(), b[:, 3:].contiguous())
@@ -193,8 +210,9 @@ def knn_points(p1: Tensor, p2: Tensor, lengths1: Optional[Tensor] = None, length
         raise ValueError('Support for 1 or 2 norm.')
     N, P1, D = p1.shape
     P2 = p2.shape[1]
-    if (p1.is_cuda and N == 1 and lengths1 is None and lengths2 is None and norm == 2 and 1 <= K <= min(16, P2) and D <= 16
-            and p1.dtype == torch.float32 and p2.dtype == torch.float32 and P1 > 0):
+    if (p1.is_cuda and N == 1 and lengths1 is None and lengths2 is None and norm == 2 and P1 > 0
+            and p1.dtype == torch.float32 and p2.dtype == torch.float32
+            and ((1 <= K <= min(16, P2) and D <= 16) or _to_point_knn(P2, D, K))):
         dists, idx = _KnnHip.apply(p1[0], p2[0], K)
         dists, idx = dists[None], (NeighbourIndex.wrap(idx[None]) if _TYPED_INDEX else idx[None])
     else:

@@ -54,9 +54,10 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 _originals = {}
+_table_originals = {}     # update_gs_knn rides with loss_weight_smooth (the `lbs_weights` group): kept beside, restored with it
 calls = {'ssim_fused': 0, 'ssim_reference': 0, 'kinematic_fused': 0, 'kinematic_reference': 0, 'sk_net_fused': 0, 'sk_net_reference': 0,
          'sp_net_fused': 0, 'sp_net_rows_fused': 0, 'sp_net_reference': 0, 'lbs_weight_fused': 0, 'lbs_weight_reference': 0, 'adam_fused': 0, 'adam_reference': 0, 'swizzle_fused': 0,
-         'weight_reg_fused': 0, 'weight_reg_reference': 0, 'adam_tiled': 0}  # counters (tests)
+         'weight_reg_fused': 0, 'weight_reg_reference': 0, 'adam_tiled': 0, 'gs_knn_fused': 0, 'gs_knn_reference': 0}  # counters (tests)
 
 
 # ------------------------------------------------------------------------------------------------ SSIM_Loss.forward
@@ -304,8 +305,8 @@ def loss_weight_sparsity(self, weight, eps=1e-7):
 
 
 def loss_weight_smooth(self, weight):
-    """``SkeletonGaussianSplatting.loss_weight_smooth`` (networks/sk_gs.py:1357-1359): the reference's own ``update_gs_knn()`` (the
-    neighbour table of the Gaussians, rebuilt by its own schedule), then value and gradient as one launch (``skgs_weight_smooth``)
+    """``SkeletonGaussianSplatting.loss_weight_smooth`` (networks/sk_gs.py:1357-1359): ``self.update_gs_knn()`` (the
+    neighbour table of the Gaussians, rebuilt by the reference's schedule -- on the device, see ``update_gs_knn`` below), then value and gradient as one launch (``skgs_weight_smooth``)
     instead of the [P, 21, K] gather and its sort-based index backward"""
     from sk_gs_amd import weight_reg as wr
     self.update_gs_knn()
@@ -315,6 +316,44 @@ def loss_weight_smooth(self, weight):
         return wr.weight_smooth(weight, nbr)
     calls['weight_reg_reference'] += 1
     return _originals['w_smooth'](self, weight)
+
+
+def _interval_due(step: int, interval: int, start=None, end=None) -> bool:
+    """``my_ext.utils.check_interval(step, interval, start, end, force_end=False)`` restated (utils.py:115-123): every ``interval`` steps
+    counted from ``start`` while ``step`` is in [start, end]; one bound alone is the END (start 0), none means no end"""
+    if start is None:
+        start, end = 0, -1
+    elif end is None:
+        start, end = 0, start
+    if interval <= 0 or step < start or (0 <= end < step):
+        return False
+    return (step - start) % interval == 0
+
+
+def update_gs_knn(self, force=False):
+    """``SkeletonGaussianSplatting.update_gs_knn`` (networks/sk_gs.py:1342-1355): the Gaussians' neighbour table ``gs_knn_index`` /
+    ``gs_knn_dist`` [P, gs_knn_num + 1], rebuilt when ``force``, when the number of Gaussians changed, or on the model's interval -- at
+    most once per step (the ``_is_gs_knn_updated`` flag).  The reference copies every position to the host, builds a KD-tree there and
+    uploads 21 columns; here a rebuild on a HIP device is ONE ``skgs_point_knn`` call on ``self.points`` where they are: no host copy,
+    no synchronisation.  Same gating, restated; anything else (CPU tensors, another dtype, more than 32 columns) is the reference's own
+    method, which then runs on the ``pykdtree`` stand-in."""
+    pts = getattr(self, 'points', None)
+    k = int(getattr(self, 'gs_knn_num', 0)) + 1
+    if not (torch.is_tensor(pts) and pts.is_cuda and pts.dtype == torch.float32 and pts.dim() == 2 and pts.shape[1] == 3
+            and pts.is_contiguous() and 1 <= k <= 32 and pts.shape[0] > 0):
+        calls['gs_knn_reference'] += 1
+        return _table_originals['gs_knn'](self, force)
+    if self._is_gs_knn_updated:
+        return
+    self._is_gs_knn_updated = True
+    if not (force or self.gs_knn_index.shape[0] != pts.shape[0]):
+        if not _interval_due(self._step, *self.gs_knn_update_interval):
+            return
+    from sk_gs_amd import _C
+    idx, dist = _C.point_knn(pts.detach(), None, K=k, want='dist')
+    self.gs_knn_index = idx if self.gs_knn_index.dtype == torch.int64 else idx.to(self.gs_knn_index.dtype)
+    self.gs_knn_dist = dist if self.gs_knn_dist.dtype == torch.float32 else dist.to(self.gs_knn_dist.dtype)
+    calls['gs_knn_fused'] += 1
 
 
 # ------------------------------------------------------------------------------------------------ render_gs_offical
@@ -663,7 +702,8 @@ def accelerate_reference(ssim: bool = True, kinematic_chain: bool = True, networ
                          adam: bool = True, swizzle: bool = True, strict: bool = True, fused_render: bool = True, joint_loss: bool = False) -> list:
     """Patch the methods on the reference's classes (the modules must be imported already; ``strict=False``: patch what IS imported,
     skip the rest -- what the post-import hook of ``install_reference_hooks(accelerate=True)`` calls as the modules arrive).  Returns what
-    was patched."""
+    was patched -- except ``SkeletonGaussianSplatting.update_gs_knn``, which is replaced together with ``loss_weight_smooth`` (its only
+    caller; group ``lbs_weights``) and is not named on its own: its original is kept in ``_table_originals``."""
     done = []
     if not strict:
         sk, ss = _fully_imported('networks.sk_gs'), _fully_imported('networks.losses.ssim')
@@ -703,6 +743,10 @@ def accelerate_reference(ssim: bool = True, kinematic_chain: bool = True, networ
             _originals['w_sparse'], _originals['w_smooth'] = mod.SkeletonGaussianSplatting.loss_weight_sparsity, mod.SkeletonGaussianSplatting.loss_weight_smooth
             mod.SkeletonGaussianSplatting.loss_weight_sparsity = loss_weight_sparsity
             mod.SkeletonGaussianSplatting.loss_weight_smooth = loss_weight_smooth
+        if 'gs_knn' not in _table_originals and hasattr(mod.SkeletonGaussianSplatting, 'update_gs_knn'):
+            # the table loss_weight_smooth reads (it calls self.update_gs_knn(): the patch rides with it and is not listed on its own)
+            _table_originals['gs_knn'] = mod.SkeletonGaussianSplatting.update_gs_knn
+            mod.SkeletonGaussianSplatting.update_gs_knn = update_gs_knn
         done += ['networks.sk_gs.SkeletonGaussianSplatting.loss_weight_sparsity', 'networks.sk_gs.SkeletonGaussianSplatting.loss_weight_smooth']
         if 'lbs_weight' not in _originals:
             _originals['lbs_weight'] = mod.SkeletonGaussianSplatting.calc_LBS_weight
@@ -798,6 +842,8 @@ def restore_reference():
     if 'w_sparse' in _originals and 'networks.sk_gs' in sys.modules:
         sys.modules['networks.sk_gs'].SkeletonGaussianSplatting.loss_weight_sparsity = _originals.pop('w_sparse')
         sys.modules['networks.sk_gs'].SkeletonGaussianSplatting.loss_weight_smooth = _originals.pop('w_smooth')
+    if 'gs_knn' in _table_originals and 'networks.sk_gs' in sys.modules:
+        sys.modules['networks.sk_gs'].SkeletonGaussianSplatting.update_gs_knn = _table_originals.pop('gs_knn')
     if 'joint_loss' in _originals and 'networks.sk_gs' in sys.modules:
         from sk_gs_amd import joint_loss as jl
         sys.modules['networks.sk_gs'].SkeletonGaussianSplatting.loss_joint_discovery = _originals.pop('joint_loss')
