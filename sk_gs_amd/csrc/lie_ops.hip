@@ -14,6 +14,10 @@
 //             :288-309 act4.  Gradients of group elements are LEFT-TANGENT row vectors in the first K of N slots, the rest zero.
 //   ToVec / FromVec backward (upstream's Python glue over orthogonal_projector, lie.h:82-90,303-311): g J and g pinv(J), the
 //             latter in closed form (J_q^T J_q = I/4 for a unit quaternion): (tau, 4 J_q (phi - t x tau)).
+// Numerics: fp32, no contraction.  so3_exp / so3_log switch to their series at lietorch's EPS = 1e-6 (well conditioned down to it).  The
+//   left Jacobian, its inverse and Q do NOT: their five coefficients are Taylor series below theta^2 = 1 and lietorch's closed forms only
+//   above (SERIES_THETA2 below) -- a deliberate departure from the reference, whose closed forms lose the gradients of exp / log and
+//   SE3.exp's translation to cancellation between 1e-6 and O(1) angles, the regime of near-identity transforms the workload lives in.
 #include "skgs_common.h"
 
 #pragma clang fp contract(off)
@@ -21,8 +25,40 @@
 namespace skgs {
 namespace lie {
 
-constexpr float EPS = 1e-6f;  // lie.h:23
+constexpr float EPS = 1e-6f;  // lie.h:23: where so3_exp / so3_log switch to their series (both are well conditioned down to it)
 constexpr float PI_F = 3.14159265358979323846f;
+
+// The five coefficients of the left Jacobian, its inverse and the coupling block Q are NOT lietorch's closed forms below
+// theta^2 = SERIES_THETA2: in fp32 those cancel between EPS and O(1) angles -- (1 - cos t) / t^2 is 0 once cosf rounds to 1, one ulp
+// of 3 t over t^5 puts Q off by 0.13 of its 0.5 at t = 1.3e-6, and at t = 0.5 the t^-4 and t^-5 coefficients are still 2e-6 off, which
+// |tau| = 100 turns into 5e-5 of a gradient row.  Below the crossover: eight terms of the Taylor series in theta^2 (the ninth is
+// < 1e-14 of the first), Horner's rule; sk_gs_amd/lietorch.py has the same numbers (SERIES_THETA2, _series_coefficients), and
+// tests/test_gpu_lie_accuracy.py holds every band from 1e-9 to pi to 3e-6 (values) / 2e-5 (gradients) per row against fp64.
+constexpr float SERIES_THETA2 = 1.0f;
+constexpr int SERIES_TERMS = 8;
+#define SKGS_F(num, den) ((float) ((num) / (den)))
+// (1 - cos t) / t^2 = sum (-1)^k t^2k / (2k + 2)!
+__device__ constexpr float SERIES_A[SERIES_TERMS] = {SKGS_F(1., 2.), SKGS_F(-1., 24.), SKGS_F(1., 720.), SKGS_F(-1., 40320.), SKGS_F(1., 3628800.),
+    SKGS_F(-1., 479001600.), SKGS_F(1., 87178291200.), SKGS_F(-1., 20922789888000.)};
+// (t - sin t) / t^3 = sum (-1)^k t^2k / (2k + 3)!
+__device__ constexpr float SERIES_B[SERIES_TERMS] = {SKGS_F(1., 6.), SKGS_F(-1., 120.), SKGS_F(1., 5040.), SKGS_F(-1., 362880.), SKGS_F(1., 39916800.),
+    SKGS_F(-1., 6227020800.), SKGS_F(1., 1307674368000.), SKGS_F(-1., 355687428096000.)};
+// (t^2 + 2 cos t - 2) / (2 t^4) = sum (-1)^k t^2k / (2k + 4)!
+__device__ constexpr float SERIES_C[SERIES_TERMS] = {SKGS_F(1., 24.), SKGS_F(-1., 720.), SKGS_F(1., 40320.), SKGS_F(-1., 3628800.), SKGS_F(1., 479001600.),
+    SKGS_F(-1., 87178291200.), SKGS_F(1., 20922789888000.), SKGS_F(-1., 6402373705728000.)};
+// (2 t - 3 sin t + t cos t) / (2 t^5) = sum (-1)^k (k + 1) t^2k / (2k + 5)!
+__device__ constexpr float SERIES_D[SERIES_TERMS] = {SKGS_F(1., 120.), SKGS_F(-2., 5040.), SKGS_F(3., 362880.), SKGS_F(-4., 39916800.), SKGS_F(5., 6227020800.),
+    SKGS_F(-6., 1307674368000.), SKGS_F(7., 355687428096000.), SKGS_F(-8., 121645100408832000.)};
+// (1 - t cot(t / 2) / 2) / t^2 = sum |B_(2k+2)| t^2k / (2k + 2)!   (Bernoulli numbers 1/6, 1/30, 1/42, 1/30, 5/66, 691/2730, 7/6, 3617/510)
+__device__ constexpr float SERIES_E[SERIES_TERMS] = {SKGS_F(1., 12.), SKGS_F(1., 720.), SKGS_F(1., 30240.), SKGS_F(1., 1209600.), SKGS_F(1., 47900160.),
+    SKGS_F(691., 1307674368000.), SKGS_F(1., 74724249600.), SKGS_F(3617., 10670622842880000.)};
+#undef SKGS_F
+__device__ __forceinline__ float series(const float (&c)[SERIES_TERMS], float t2) {
+  float r = c[SERIES_TERMS - 1];
+#pragma unroll
+  for (int k = SERIES_TERMS - 2; k >= 0; --k) r = r * t2 + c[k];
+  return r;
+}
 
 struct V3 {
   float x, y, z;
@@ -139,22 +175,24 @@ __device__ __forceinline__ V3 so3_log(Quat q) {
 __device__ __forceinline__ M3 so3_left_jacobian(V3 phi) {
   const M3 Phi = hat(phi);
   const float theta2 = dot(phi, phi), theta = sqrtf(theta2);
-  const float c1 = theta < EPS ? 0.5f - (1.0f / 24.0f) * theta2 : (1.0f - cosf(theta)) / theta2;
-  const float c2 = theta < EPS ? 1.0f / 6.0f - (1.0f / 120.0f) * theta2 : (theta - sinf(theta)) / (theta2 * theta);
+  const bool small = theta2 < SERIES_THETA2;
+  const float c1 = small ? series(SERIES_A, theta2) : (1.0f - cosf(theta)) / theta2;
+  const float c2 = small ? series(SERIES_B, theta2) : (theta - sinf(theta)) / (theta2 * theta);
   return add(add(eye(), Phi, c1), mm(Phi, Phi), c2);
 }
 __device__ __forceinline__ M3 so3_left_jacobian_inverse(V3 phi) {
   const M3 Phi = hat(phi);
-  const float theta = sqrtf(dot(phi, phi)), half = 0.5f * theta;
-  const float c2 = theta < EPS ? 1.0f / 12.0f : (1.0f - theta * cosf(half) / (2.0f * sinf(half))) / (theta * theta);
+  const float theta2 = dot(phi, phi), theta = sqrtf(theta2), half = 0.5f * theta;
+  const float c2 = theta2 < SERIES_THETA2 ? series(SERIES_E, theta2) : (1.0f - theta * cosf(half) / (2.0f * sinf(half))) / theta2;
   return add(add(eye(), Phi, -0.5f), mm(Phi, Phi), c2);
 }
 __device__ __forceinline__ M3 se3_calcQ(V3 tau, V3 phi) {
   const M3 Tau = hat(tau), Phi = hat(phi);
-  const float theta = sqrtf(dot(phi, phi)), t2 = theta * theta, t4 = t2 * t2;
-  const float c1 = theta < EPS ? 1.0f / 6.0f - (1.0f / 120.0f) * t2 : (theta - sinf(theta)) / (t2 * theta);
-  const float c2 = theta < EPS ? 1.0f / 24.0f - (1.0f / 720.0f) * t2 : (t2 + 2.f * cosf(theta) - 2.f) / (2.f * t4);
-  const float c3 = theta < EPS ? 1.0f / 120.0f - (1.0f / 2520.0f) * t2 : (2.f * theta - 3.f * sinf(theta) + theta * cosf(theta)) / (2.f * t4 * theta);
+  const float t2 = dot(phi, phi), theta = sqrtf(t2), t4 = t2 * t2;
+  const bool small = t2 < SERIES_THETA2;
+  const float c1 = small ? series(SERIES_B, t2) : (theta - sinf(theta)) / (t2 * theta);
+  const float c2 = small ? series(SERIES_C, t2) : (t2 + 2.f * cosf(theta) - 2.f) / (2.f * t4);
+  const float c3 = small ? series(SERIES_D, t2) : (2.f * theta - 3.f * sinf(theta) + theta * cosf(theta)) / (2.f * t4 * theta);
   const M3 PT = mm(Phi, Tau), TP = mm(Tau, Phi), PTP = mm(PT, Phi);
   M3 q = scale(0.5f, Tau);
   q = add(q, add(add(PT, TP), PTP), c1);

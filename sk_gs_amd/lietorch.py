@@ -51,7 +51,41 @@ from torch import Tensor
 
 __all__ = ['SO3', 'SE3', 'LieGroup', 'LieGroupParameter', 'cat', 'stack']
 
-EPS = 1e-6  # lie.h:23
+EPS = 1e-6  # lie.h:23: where so3_exp / so3_log switch to their series (both are well conditioned down to it)
+
+# The five coefficients of the left Jacobian, its inverse and SE3's coupling block Q are NOT evaluated by lietorch's closed forms below
+# theta^2 = SERIES_THETA2: in fp32 those cancel between lie.h's EPS and O(1) angles ((1 - cos t) / t^2 is 0 once cos rounds to 1; one
+# ulp of 3 t over t^5 puts Q off by 0.13 of its 0.5 at t = 1.3e-6; at t = 0.5 the closed forms of the t^-4 and t^-5 coefficients are
+# still off by 2e-6, which |tau| = 100 turns into 5e-5 of a gradient row).  Below the crossover: SERIES_TERMS terms of the Taylor series
+# in theta^2, lowest order first; the first term left out is < 1e-14 at the crossover, so the fp64 path keeps its precision as well
+# (tests/test_lie_accuracy_cpu.py holds both sides of the crossover to the bounds).  csrc/lie_ops.hip has the same numbers.
+SERIES_THETA2 = 1.0
+SERIES_TERMS = 8
+
+
+def _series_coefficients(n):
+    from fractions import Fraction
+    from math import factorial
+    bern = [Fraction(1)]                                                         # Bernoulli numbers B_0 .. B_2n
+    for m in range(1, 2 * n + 1):
+        bern.append(-sum(Fraction(factorial(m + 1), factorial(k) * factorial(m + 1 - k)) * bern[k] for k in range(m)) / (m + 1))
+    sign = lambda k: -1 if k % 2 else 1  # noqa: E731
+    return (tuple(float(Fraction(sign(k), factorial(2 * k + 2))) for k in range(n)),            # A = (1 - cos t) / t^2
+            tuple(float(Fraction(sign(k), factorial(2 * k + 3))) for k in range(n)),            # B = (t - sin t) / t^3
+            tuple(float(Fraction(sign(k), factorial(2 * k + 4))) for k in range(n)),            # C = (t^2 + 2 cos t - 2) / (2 t^4)
+            tuple(float(Fraction(sign(k) * (k + 1), factorial(2 * k + 5))) for k in range(n)),  # D = (2 t - 3 sin t + t cos t) / (2 t^5)
+            tuple(float(abs(bern[2 * k + 2]) / factorial(2 * k + 2)) for k in range(n)))        # E = (1 - t cot(t / 2) / 2) / t^2
+
+
+_SERIES_A, _SERIES_B, _SERIES_C, _SERIES_D, _SERIES_E = _series_coefficients(SERIES_TERMS)
+
+
+def _series(c, t2: Tensor) -> Tensor:
+    """c[0] + c[1] t2 + c[2] t2^2 + ... by Horner's rule"""
+    r = torch.full_like(t2, c[-1])
+    for ck in c[-2::-1]:
+        r = r * t2 + ck
+    return r
 
 
 # ------------------------------------------------------------------------------------------------ small batched helpers
@@ -140,23 +174,23 @@ def _so3_left_jacobian(phi: Tensor) -> Tensor:
     I = torch.eye(3, dtype=phi.dtype, device=phi.device)
     Phi = _hat(phi)
     theta2 = phi.square().sum(dim=-1)[..., None, None]
-    theta = theta2.sqrt()
-    small = theta < EPS
+    small = theta2 < SERIES_THETA2
     safe2 = torch.where(small, torch.ones_like(theta2), theta2)
-    safe = torch.where(small, torch.ones_like(theta), theta)
-    c1 = torch.where(small, 0.5 - (1.0 / 24.0) * theta2, (1.0 - torch.cos(safe)) / safe2)
-    c2 = torch.where(small, 1.0 / 6.0 - (1.0 / 120.0) * theta2, (safe - torch.sin(safe)) / (safe2 * safe))
+    safe = safe2.sqrt()
+    c1 = torch.where(small, _series(_SERIES_A, theta2), (1.0 - torch.cos(safe)) / safe2)
+    c2 = torch.where(small, _series(_SERIES_B, theta2), (safe - torch.sin(safe)) / (safe2 * safe))
     return I + c1 * Phi + c2 * (Phi @ Phi)
 
 
 def _so3_left_jacobian_inverse(phi: Tensor) -> Tensor:
     I = torch.eye(3, dtype=phi.dtype, device=phi.device)
     Phi = _hat(phi)
-    theta = phi.square().sum(dim=-1).sqrt()[..., None, None]
-    small = theta < EPS
-    safe = torch.where(small, torch.ones_like(theta), theta)
+    theta2 = phi.square().sum(dim=-1)[..., None, None]
+    small = theta2 < SERIES_THETA2
+    safe2 = torch.where(small, torch.ones_like(theta2), theta2)
+    safe = safe2.sqrt()
     half = 0.5 * safe
-    c2 = torch.where(small, torch.full_like(theta, 1.0 / 12.0), (1.0 - safe * torch.cos(half) / (2.0 * torch.sin(half))) / (safe * safe))
+    c2 = torch.where(small, _series(_SERIES_E, theta2), (1.0 - safe * torch.cos(half) / (2.0 * torch.sin(half))) / safe2)
     return I - 0.5 * Phi + c2 * (Phi @ Phi)
 
 
@@ -183,15 +217,13 @@ def _se3_adj(t: Tensor, q: Tensor) -> Tensor:
 
 def _se3_calcQ(tau: Tensor, phi: Tensor) -> Tensor:
     Tau, Phi = _hat(tau), _hat(phi)
-    theta = phi.square().sum(dim=-1).sqrt()[..., None, None]
-    t2 = theta * theta
-    t4 = t2 * t2
-    small = theta < EPS
-    s = torch.where(small, torch.ones_like(theta), theta)
-    s2, s4 = s * s, s * s * s * s
-    c1 = torch.where(small, 1.0 / 6.0 - (1.0 / 120.0) * t2, (s - torch.sin(s)) / (s2 * s))
-    c2 = torch.where(small, 1.0 / 24.0 - (1.0 / 720.0) * t2, (s2 + 2 * torch.cos(s) - 2) / (2 * s4))
-    c3 = torch.where(small, 1.0 / 120.0 - (1.0 / 2520.0) * t2, (2 * s - 3 * torch.sin(s) + s * torch.cos(s)) / (2 * s4 * s))
+    t2 = phi.square().sum(dim=-1)[..., None, None]
+    small = t2 < SERIES_THETA2
+    s2 = torch.where(small, torch.ones_like(t2), t2)
+    s, s4 = s2.sqrt(), s2 * s2
+    c1 = torch.where(small, _series(_SERIES_B, t2), (s - torch.sin(s)) / (s2 * s))
+    c2 = torch.where(small, _series(_SERIES_C, t2), (s2 + 2 * torch.cos(s) - 2) / (2 * s4))
+    c3 = torch.where(small, _series(_SERIES_D, t2), (2 * s - 3 * torch.sin(s) + s * torch.cos(s)) / (2 * s4 * s))
     PT, TP = Phi @ Tau, Tau @ Phi
     PTP = PT @ Phi
     return (0.5 * Tau + c1 * (PT + TP + PTP) + c2 * (Phi @ PT + TP @ Phi - 3 * PTP) + c3 * (PTP @ Phi + Phi @ PTP))
