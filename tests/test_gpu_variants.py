@@ -186,15 +186,20 @@ def test_render_dict_other_extras_and_detach(oracle32):
     assert tuple(idx.shape) == (H, W, 2) and tuple(w.shape) == (H, W, 2)
 
 
-@pytest.mark.parametrize('P', [2000, 3, 1, 50_001])
+@pytest.mark.parametrize('P', [2000, 3, 1, 50_001, 4, 5, 256, 257, 513, 'duplicates'])
 def test_simple_knn_under_its_pybind_name(P):
     """``simple_knn`` (my_ext/_C/src/other/knn.cu:192-205; what create_from_pcd resolves, gaussian_splatting.py:211-213): the mean
     squared distance to the three nearest OTHER points, against a brute-force restatement (exact three smallest of the same
-    fp32 distances; fewer than four points: missing neighbours count as FLT_MAX, as upstream)"""
+    fp32 distances; fewer than four points: missing neighbours count as FLT_MAX, as upstream -- nothing finite to compare there;
+    from four points on every value is finite and compared).  'duplicates': 300 points drawn from 100 positions, so the nearest
+    neighbours of most points are copies of themselves at distance 0 -- only the point's own index may be skipped."""
     from sk_gs_amd import _C
     m = _C.pybind_module()
+    duplicates, P = P == 'duplicates', 300 if P == 'duplicates' else P
     g = torch.Generator().manual_seed(P)
     pts = (torch.rand(P, 3, generator=g) * 2.6 - 1.3).cuda()
+    if duplicates:
+        pts = pts[:100][torch.randint(0, 100, (P,), generator=g).cuda()].contiguous()
     got = getattr(m, 'simple_knn')(pts)
     assert tuple(got.shape) == (P,) and got.dtype == torch.float32
     n = min(P, 4000)  # (the check is O(n P) on the host)
@@ -206,6 +211,10 @@ def test_simple_knn_under_its_pybind_name(P):
         best = torch.cat([best, torch.full((n, 3 - best.shape[1]), 3.402823466e+38, device='cuda')], 1)
     want = (best[:, 0] + best[:, 1] + best[:, 2]) / 3.0
     finite = torch.isfinite(want) & (want < 1e30)
+    if P >= 4:
+        assert bool(finite[:n].all())                        # every row is compared
+    if duplicates:
+        assert bool((want == 0).any()) and bool((want > 0).any())
     assert rel_err_t(got[:n][finite], want[finite]) <= 1e-5
     with pytest.raises(_C.SkgsError):
         m.simple_knn(pts.cpu())
